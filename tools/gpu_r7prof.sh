@@ -10,12 +10,14 @@ mkdir -p gpurun_out
 TAG=${1:-r7}
 DOM=${DOM:-bwd:d_out0}
 timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 --cpu-seconds 15 \
+    --full \
     --profile-ops gpurun_out/ops_$TAG.txt > gpurun_out/bench_$TAG.log 2>&1 \
     || { tail -30 gpurun_out/bench_$TAG.log; exit 1; }
 tail -1 gpurun_out/bench_$TAG.log
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG -o run --output-format csv \
     -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-infer \
+    --full \
     --no-dense-leg --no-dp-leg --dominant $DOM \
     > $GRAFT_REPO_ROOT/gpurun_out/bench_prof_$TAG.log 2>&1 || { tail -30 $GRAFT_REPO_ROOT/gpurun_out/bench_prof_$TAG.log; exit 1; }
 tail -1 $GRAFT_REPO_ROOT/gpurun_out/bench_prof_$TAG.log

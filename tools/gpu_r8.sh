@@ -17,6 +17,7 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun
 tail -2 gpurun_out/smoke_$TAG.log
 fi
 timeout -k 10 500 python -u bench.py --steps 20 --warmup 5 --cpu-seconds 15 \
+    --full \
     --profile-ops gpurun_out/ops_$TAG.txt > gpurun_out/bench_$TAG.log 2>&1 \
     || { tail -30 gpurun_out/bench_$TAG.log; exit 1; }
 tail -1 gpurun_out/bench_$TAG.log
@@ -28,6 +29,7 @@ cat gpurun_out/rh_graph_$TAG.log gpurun_out/rh_eager_$TAG.log
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG -o run --output-format csv \
     -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-infer \
+    --full \
     --no-dense-leg --no-dp-leg --dominant ${DOM:-bwd:d_out0} \
     > $GRAFT_REPO_ROOT/gpurun_out/bench_prof_$TAG.log 2>&1 || { tail -30 $GRAFT_REPO_ROOT/gpurun_out/bench_prof_$TAG.log; exit 1; }
 tail -1 $GRAFT_REPO_ROOT/gpurun_out/bench_prof_$TAG.log
