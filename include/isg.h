@@ -321,7 +321,10 @@ int32_t isg_grad_finalize(const isg_grad_final* items, int32_t nitems, isg_strea
  * the running statistics of the `nbnu` BatchNorm layers (isg_bn_update_running). `gf` and
  * `bnu` are DEVICE arrays. owner[i]: bit 0 = Adam updates element i (a used parameter),
  * bit 1 = a grad_final item writes grad[i] (the fold skips it). Bitwise the result of those
- * separate calls. hyper = (lr, beta1, beta2, eps, weight_decay), device doubles. */
+ * separate calls for every item form (a grad_final item may read a gamma that its own
+ * dgamma element's Adam updates: it reads before it writes); an eval-mode (train 0) item
+ * must not read the running statistics of a layer in `bnu`.
+ * hyper = (lr, beta1, beta2, eps, weight_decay), device doubles. */
 typedef struct {
     float* grad;
     const double* rep;         /* nrep replicas, replica stride n */

@@ -641,12 +641,15 @@ ISG_DEV void grad_final_item(const isg_grad_final& f, Put put) {
         const double gs = rep_sum(f.stats, 4 * f.C, 2 * f.C + c);
         const double gxs = rep_sum(f.stats, 4 * f.C, 3 * f.C + c);  // sum g*(y - mean), centred
         const double dgamma = rstd * gxs;
-        if (f.dgamma) put(f.dgamma + c, (float)dgamma);
-        if (f.dbeta) put(f.dbeta + c, (float)gs);
+        // Every value is computed before the first put: in the fused step tail a put also
+        // runs Adam on the element it stores, and there dgamma's element is gamma's own
+        // (the flat gradient and the flat parameters share offsets), so a gamma read after
+        // put(dgamma) would see the updated parameter where the separate launches (all of
+        // grad_final, then Adam) see the old one.
+        double db = 0.0;
         if (f.dconv_bias) {
             // sum over pixels of dy = A*g + B*(y-mean) + C  (BatchNorm backward)
             const double gam = (double)f.gamma[c];
-            double db;
             if (f.train) {
                 const double sy = rep_sum(f.stats, 4 * f.C, c);
                 const double mg = gs / M, mgx = rstd * gxs / M;
@@ -654,8 +657,10 @@ ISG_DEV void grad_final_item(const isg_grad_final& f, Put put) {
             } else {
                 db = gam * rstd * gs;
             }
-            put(f.dconv_bias + c, (float)db);
         }
+        if (f.dgamma) put(f.dgamma + c, (float)dgamma);
+        if (f.dbeta) put(f.dbeta + c, (float)gs);
+        if (f.dconv_bias) put(f.dconv_bias + c, (float)db);
     }
 }
 
@@ -851,6 +856,14 @@ __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, co
 // device functions), so the result is bitwise that of the separate launches, which ran as
 // 1 + 5 + 1 (+1 step counter) launches hopping between streams, plus 3 BN-update launches
 // on the forward's critical path.
+// Why one launch may interleave what the separate launches ordered (all gradients, then
+// Adam): Adam on element i reads and writes only param/exp_avg/exp_avg_sq[i] and grad[i]'s
+// value, and each element has one writer (the fold, or the one grad_final item that owns
+// it). The only parameter any workgroup READS is a grad_final item's gamma, whose element
+// that same item's dgamma put updates: grad_final_item therefore reads it, with everything
+// else, before its first put. The fold reads replicas only; bn_update_item reads statistics
+// and reads/writes running statistics, which no Adam touches (an eval-mode grad_final item
+// reads running statistics: it must not name a layer that `bnu` updates in the same call).
 template <int NREP>
 __global__ __launch_bounds__(kThreads) void step_tail_kernel(isg_step_tail_args a, int nfold) {
     const int b = blockIdx.x;

@@ -202,6 +202,8 @@ class Trainer:
         # a captured graph follows load_optimizer_state_dict), the owner mask (bit 0: Adam
         # updates the element, bit 1: a grad_final item writes its gradient)
         self.hyper = torch.tensor(self._hyper_vec(), dtype=torch.float64, device=dev)
+        # the attribute values self.hyper was filled from (step() follows an assigned lr)
+        self._hyper_filled = (self.lr, tuple(self.betas), self.eps, self.wd)
         owner = live.clone()
         for off, cnt in self.plan.tail_owned:
             owner[off:off + cnt] |= 2
@@ -408,6 +410,7 @@ class Trainer:
         stays in loss_acc for loss())."""
         if self.device.type != "cuda":
             raise RuntimeError("Trainer.step runs on the MI355X only (no CPU path)")
+        self._sync_hyper()
         if x is not None:
             for dst, src in zip(self.inputs, x):
                 dst.copy_(src, non_blocking=True)
@@ -481,10 +484,20 @@ class Trainer:
                 assert st["exp_avg"].shape == params[i].shape
         self.step_dev.fill_(max(steps) if steps else 0)
         self.step_count = max(steps) if steps else 0
+        self._sync_hyper(force=True)
+
+    def _sync_hyper(self, force=False):
+        """Make the step use the hyperparameters the attributes hold now (lr, betas, eps,
+        wd: assigned directly, or loaded): a tuple comparison per step, device work only
+        when something changed. The fused tail reads them from the device tensor `hyper`
+        (a captured graph follows it); isg_adam_dev takes them by value, so a captured
+        unfused step holds the old ones and is re-recorded."""
+        raw = (self.lr, tuple(self.betas), self.eps, self.wd)
+        if not force and raw == self._hyper_filled:
+            return
         self.hyper.copy_(torch.tensor(self._hyper_vec(), dtype=torch.float64))
-        # isg_adam_dev takes lr/betas/eps/wd by value, so a captured graph holds the old
-        # ones: re-record the step when the loaded hyperparameters differ
-        if self.graphs and self._captured[1] != self._hyper():
+        self._hyper_filled = raw
+        if self.graphs and not self.fused_tail and self._captured[1] != self._hyper():
             self.capture(split=self._captured[0])
 
     def load_state_dict(self, sd):

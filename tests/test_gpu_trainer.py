@@ -323,24 +323,55 @@ def test_bn_final_launches_match_default(monkeypatch):
         assert err <= 1e-5 * scale, (i, err)
 
 
-@pytest.mark.parametrize("graph", [True, False], ids=["graph", "eager"])
-def test_fused_step_tail_matches_separate_launches(graph):
+def _dconv_bias_ranges(tr):
+    """(offset, count) in the flat gradient of every dconv_bias output of the fused tail's
+    grad_final items (a subset of plan.tail_owned), read from the item table's pointer
+    fix-ups (engine.Record: body = ListRec header + items, fix = (byte, slot, offset))."""
+    import ctypes
+    import struct
+    from instancesegmentation_amd import _lib as L
+    rec = tr.plan.tail_gf
+    base, isz = ctypes.sizeof(L.ListRec), ctypes.sizeof(L.GradFinal)
+    out = []
+    for loc, _, off in rec.fix:
+        i, field = divmod(loc - base, isz)
+        if field == L.GradFinal.dconv_bias.offset:
+            (C,) = struct.unpack_from("<i", rec.body, base + i * isz + L.GradFinal.C.offset)
+            out.append((off // 4, C))
+    assert set(out) <= set(tr.plan.tail_owned)
+    return out
+
+
+@pytest.mark.parametrize("graph,h,w", [(True, 256, 256), (False, 256, 256), (True, 96, 160),
+                                       (False, 96, 160)],
+                         ids=["graph", "eager", "graph-96x160", "eager-96x160"])
+def test_fused_step_tail_matches_separate_launches(graph, h, w):
     """The world-1 step's fused tail (isg.h isg_step_tail: replica fold + gradient
     finalisation + Adam + BatchNorm running statistics in one launch, the step counter
     advanced on the side stream) against the separate launches it replaces (OP_SUM_REP,
     the OP_GRAD_FINAL lists, isg_adam_dev, the forward's OP_BN_UPDATE lists): over three
     steps on the keypoint path, the flat gradient, parameters, both Adam moments, the
-    running statistics and the step counter are bit-identical."""
+    running statistics and the step counter are bit-identical.
+
+    At 2x256x256 every BatchNorm count is a power of two, so the gradient of a conv bias
+    ahead of a train-mode BatchNorm (the rounding residue of a mathematically zero
+    expression that also reads gamma) is exactly 0 whatever gamma is read. At 2x96x160 the
+    counts are 15*2^k and the residues are not zero: that case sees a fused tail that reads
+    a gamma its own Adam has already updated (it failed before grad_final_item read gamma
+    ahead of its first store), and asserts that it cannot go vacuous again."""
     from instancesegmentation_amd.data import device_batch
     torch.manual_seed(321)
     init = Segment(20).state_dict()
-    xs, mask = device_batch(2, 256, 256, DEV, seed=77, keypoints=True)
+    xs, mask = device_batch(2, h, w, DEV, seed=77, keypoints=True)
+    cb_ranges = []
 
     def run(fused):
         m = Segment(20)
         m.load_state_dict(init)
         tr = Trainer(m, 2, [tuple(x.shape) for x in xs], device=DEV, fused_tail=fused)
         assert tr.fused_tail == fused
+        if fused:
+            cb_ranges.extend(_dconv_bias_ranges(tr))
         if graph:
             tr.capture()
         out = []
@@ -352,6 +383,12 @@ def test_fused_step_tail_matches_separate_launches(graph):
         return out, tr.loss()
 
     (a, la), (b, lb) = run(True), run(False)
+    if (h, w) != (256, 256):
+        assert cb_ranges
+        nz = sum(int((b[0][0][off:off + cnt] != 0).sum()) for off, cnt in cb_ranges)
+        print(f"{h}x{w}: {nz} non-zero conv-bias gradient elements in {len(cb_ranges)} "
+              "dconv_bias ranges (separate launches, step 1)")
+        assert nz > 0, "every dconv_bias element is 0: the parity check is blind to the gamma read"
     names = ("grad", "params", "exp_avg", "exp_avg_sq", "running stats", "step")
     for k, (sa, sb) in enumerate(zip(a, b)):
         diff = [int((u != v).sum()) for u, v in zip(sa, sb)]
@@ -359,3 +396,72 @@ def test_fused_step_tail_matches_separate_launches(graph):
         assert diff == [0] * 6, (k, diff)
     assert int(a[-1][5].item()) == 3
     assert abs(la - lb) <= 1e-12 * max(1.0, abs(lb))
+
+
+@pytest.mark.parametrize("captured", [False, True], ids=["eager", "graph"])
+@pytest.mark.parametrize("fused", [True, False], ids=["fused", "separate"])
+def test_assigned_hyperparameters_reach_the_step(fused, captured):
+    """`trainer.lr = ...` between steps must reach the next step in every form of it: the
+    fused tail reads Adam's hyperparameters from a device tensor (refreshed by step() when
+    the attributes changed), the separate isg_adam_dev launch takes them by value (a
+    captured step is re-recorded). lr 0 leaves every parameter bit-identical; lr 1e-3
+    moves them again."""
+    fx = SegmentFixture("segment20_n2_128.npz")
+    tr = Trainer(_model(fx), fx.n, [(fx.n, 3, fx.h, fx.w), (fx.n, 17, fx.h, fx.w)], device=DEV,
+                 fused_tail=fused)
+    assert tr.fused_tail == fused
+    if captured:
+        tr.capture()
+    xs, y = _inputs(fx.x), torch.from_numpy(fx.mask).to(DEV)
+    tr.step(xs, y)
+    torch.cuda.synchronize()
+    before = tr.flat.clone()
+    tr.lr = 0.0
+    tr.step(xs, y)
+    torch.cuda.synchronize()
+    assert torch.equal(tr.flat, before)
+    tr.lr = 1e-3
+    tr.step(xs, y)
+    torch.cuda.synchronize()
+    assert not torch.equal(tr.flat, before)
+    assert int(tr.step_dev.item()) == 3
+
+
+@pytest.mark.parametrize("switch", ["ISG_NO_TAIL_FOLD", "ISG_NO_DW_FUSE"])
+def test_plan_switches_match_default(monkeypatch, switch):
+    """The two plan switches read at plan-build time — ISG_NO_TAIL_FOLD=1 (residual tails
+    run as their own launches instead of folded into their consumers) and ISG_NO_DW_FUSE=1
+    (a depthwise layer's two backward halves as two launches instead of isg_depthwise_bwd) —
+    must give the default plan's gradients: within the bar for alternative plans,
+    1e-5 x max|grad|, over three replays. isg.h promises the fused depthwise backward is
+    bitwise the two calls: ISG_NO_DW_FUSE is held to exact equality."""
+    fx = SegmentFixture("segment20_n2_128.npz")
+    xs, y = _inputs(fx.x), torch.from_numpy(fx.mask).to(DEV)
+
+    def grads(env):
+        for k in ("ISG_NO_TAIL_FOLD", "ISG_NO_DW_FUSE"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        tr = Trainer(_model(fx), fx.n, [(fx.n, 3, fx.h, fx.w), (fx.n, 17, fx.h, fx.w)],
+                     device=DEV).capture()
+        sd = tr.optimizer_state_dict()
+        sd["param_groups"][0]["lr"] = 0.0  # parameters fixed: every replay has one answer
+        tr.load_optimizer_state_dict(sd)
+        out = []
+        for _ in range(3):
+            tr.step(xs, y)
+            torch.cuda.synchronize()
+            out.append(tr.grad_flat.detach().cpu().clone())
+        return out
+
+    base = grads({})[0]
+    scale = base.abs().max().item()
+    for i, g in enumerate(grads({switch: "1"})):
+        err = (g.double() - base.double()).abs().max().item()
+        nbits = int((g != base).sum())
+        print(f"{switch}=1 replay {i}: max abs diff {err:.2e} (scale {scale:.2e}), "
+              f"{nbits} of {g.numel()} elements differ bitwise")
+        assert err <= 1e-5 * scale, (switch, i, err)
+        if switch == "ISG_NO_DW_FUSE":
+            assert nbits == 0, (switch, i, nbits)
