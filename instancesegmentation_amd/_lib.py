@@ -20,7 +20,7 @@ SINK_STORE, SINK_ACCUM, SINK_ACTBWD, SINK_NONE = 0, 1, 2, 3
 MAX_SEGS = 3
 LIST_CHUNK = 32
 STAT_REP = int(os.environ.get("ISG_STAT_REP", "4"))  # accumulator replicas (isg.h ISG_STAT_REP)
-ABI_VERSION = 11
+ABI_VERSION = 12
 WREP = int(os.environ.get("ISG_WREP", "16"))  # weight-gradient replicas (isg.h ISG_WREP)
 
 
@@ -225,6 +225,9 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p]),
     "isg_mask_paste_nms": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isg_mask_rle_workspace": (c_int64, [c_int32, c_int32, c_int32]),
+    "isg_mask_rle": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                               c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "isg_instance_crop": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                     c_int32, c_void_p, c_void_p]),
     "isg_keypoint_heatmaps": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_double,

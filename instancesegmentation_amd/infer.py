@@ -17,6 +17,8 @@ per-instance input path (train_instance.py:139-202, test branch) and model:
   masks    = paste back through the window onto the image canvas (A13), uint8 by
              truncation of p*255 (tensor2mask, train_instance.py:398-399)
   keep     = greedy mask-NMS, IoU 0.5 (A14)
+  rle      = (rle=True) the kept masks run-length encoded on the GPU, COCO order
+             (csrc/mask_rle.hip, rle.py): a few KB leave the device instead of the canvases
 
 Everything after the host copy of the image runs on the GPU (csrc/infer_ops.hip,
 maskops.hip, the Segment plan) and is captured into one HIP graph per (image size,
@@ -25,40 +27,56 @@ which produce empty masks, score 0, and never suppress anything; their indices a
 dropped from `keep`.
 
     python -m instancesegmentation_amd.infer -i IMAGES -o OUT [--continue-test]
-        [--checkpoint best.pth] [--max-instances 16]
+        [--checkpoint best.pth] [--max-instances 16] [--format {png,coco}]
 
 Instances come from a sidecar annotation next to each image (`<name>.json`, the common
 dataset format of dataset/transfer_coco.py:125-227: {"object": [{"box": [x0,y0,x1,y1],
 "body_keypoint": {part: {"status": "vis", "point": [x, y]}}}]}; keys may carry ymlib
 `key_combine` suffixes, see data.py). Output per image: `<out>/<name>/<i>.png` for each
-kept instance and `<out>/<name>.json` with the kept indices and scores.
+kept instance and `<out>/<name>.json` with the kept indices and scores. With
+`--format coco` no PNG is written: `<out>/<name>.json` also carries one COCO RLE
+("segmentation") and one box ("bbox", [x, y, w, h]) per kept index, and
+`<out>/results.json` is the COCO results list assembled from every per-image JSON in
+the output directory (so `--continue-test` completes it).
 """
 import argparse
 import ctypes
 import glob
 import json
 import os
+import warnings
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import rle as R
 from .engine import S_ACT, S_IN, S_OUT, S_STATS, S_TENSOR0, Plan
 
 CROP = 480   # train_instance.py:77
 PAD = 16     # train_instance.py:167
 N_PARTS = 17
 NMS_MAX = 256  # masks one isg_mask_nms launch can rank (include/isg.h)
+# default capacity of the RLE buffer, in uint32 counts: RLE_CAPACITY_FACTOR * K * (H + W).
+# A mask has one count per boundary crossing of a column, so a convex blob that fills the
+# frame has about 2 W of them and a person (limbs, holes) a small multiple of that (a
+# 1024^2 ellipse: 1,199 counts against the 32,768 a slot gets here). Noise can still
+# exceed any fixed capacity (a checkerboard has H*W + 1 counts): result_rle() then
+# falls back to the CPU encoder for the slots that did not fit.
+RLE_CAPACITY_FACTOR = 16
 
 
 class InstanceSegmenter:
     """Segment(20) inference over the instances of one image, as one HIP graph.
 
     model: a Segment(20) whose weights are loaded (it is deep-copied and fused);
-    image_hw: (H, W) of the images this instance serves; max_instances: capacity K."""
+    image_hw: (H, W) of the images this instance serves; max_instances: capacity K.
+    rle=True appends the COCO run-length encoding of the kept masks to the pipeline
+    (result_rle()); rle_capacity: uint32 counts the device buffer holds for all kept masks
+    of one image (default RLE_CAPACITY_FACTOR * K * (H + W))."""
 
     def __init__(self, model, image_hw, max_instances=16, iou_thr=0.5, device=None,
-                 capture=True):
+                 capture=True, rle=False, rle_capacity=None):
         import copy
         self.device = torch.device(device or "cuda")
         if self.device.type != "cuda":
@@ -89,6 +107,17 @@ class InstanceSegmenter:
         self.scores = torch.empty(K, dtype=torch.float32, device=dev)
         self.keep = torch.empty(K, dtype=torch.int32, device=dev)
         self.nkeep = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.rle = bool(rle)
+        if self.rle:
+            cap = RLE_CAPACITY_FACTOR * K * (H + W) if rle_capacity is None else int(rle_capacity)
+            if cap < 0:
+                raise ValueError(f"rle_capacity {cap} < 0")
+            self.rle_capacity = cap
+            self.rle_runs = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)  # uint32 bits
+            self.rle_offsets = torch.empty(K + 1, dtype=torch.int64, device=dev)
+            self.rle_work = torch.empty(L.lib().isg_mask_rle_workspace(K, H, W),
+                                        dtype=torch.uint8, device=dev)
+            self._rle_warned = False
         self.act = torch.empty(max(self.plan.act_size, 1), dtype=torch.float32, device=dev)
         self.stats = torch.empty(self.plan.stats_size, dtype=torch.float64, device=dev)
         g = self.plan.graph
@@ -127,6 +156,12 @@ class InstanceSegmenter:
                                        self.work.data_ptr(), self.scores.data_ptr(),
                                        self.keep.data_ptr(), self.nkeep.data_ptr(), st),
                 "mask_paste_nms")
+        if self.rle:  # the kept masks, in keep order
+            L.check(lib.isg_mask_rle(self.masks.data_ptr(), K, self.H, self.W,
+                                     self.keep.data_ptr(), self.nkeep.data_ptr(), K,
+                                     self.rle_runs.data_ptr(), self.rle_capacity,
+                                     self.rle_offsets.data_ptr(), self.rle_work.data_ptr(), st),
+                    "mask_rle")
 
     def load(self, image, boxes, keypoints):
         """Copy one image's inputs into the static buffers (no launch).
@@ -167,6 +202,40 @@ class InstanceSegmenter:
         nk = int(self.nkeep.item())
         keep = [int(i) for i in self.keep[:nk].cpu().tolist() if i < self.n]
         return self.masks[:self.n], keep, self.scores[:self.n].cpu().numpy()
+
+    def result_rle(self):
+        """(segmentations, keep list, scores [n]) of the last run: segmentations[i] is the
+        COCO RLE {"size": [H, W], "counts": str} of mask keep[i]. Only the offsets and the
+        counts themselves leave the device. If the counts of an image exceed rle_capacity,
+        the masks that did not fit are encoded on the CPU from their canvases (same
+        answer, one warning)."""
+        if not self.rle:
+            raise RuntimeError("result_rle() needs InstanceSegmenter(rle=True)")
+        K = self.K
+        torch.cuda.synchronize(self.device)  # as result() does, before anything reads
+        # the small results in one copy: offsets, keep, nkeep, scores
+        meta = torch.cat([self.rle_offsets.view(torch.int32), self.keep, self.nkeep,
+                          self.scores.view(torch.int32)]).cpu().numpy()
+        off = meta[:2 * K + 2].view(np.int64)
+        slots = meta[2 * K + 2:3 * K + 2][:int(meta[3 * K + 2])].tolist()
+        scores = meta[3 * K + 3:].view(np.float32)[:self.n].copy()
+        total, cap = int(off[-1]), self.rle_capacity
+        runs = self.rle_runs[:min(total, cap)].cpu().numpy().view(np.uint32)
+        if total > cap and not self._rle_warned:
+            self._rle_warned = True
+            warnings.warn(f"RLE buffer overflow: {total} counts > rle_capacity {cap}; the "
+                          "masks that did not fit are encoded on the CPU", RuntimeWarning)
+        segs, keep = [], []
+        for j, i in enumerate(slots):
+            if i >= self.n:  # padded slot
+                continue
+            if off[j + 1] <= cap:
+                counts = runs[off[j]:off[j + 1]]
+            else:
+                counts = R.encode(self.masks[i].cpu().numpy())
+            segs.append({"size": [self.H, self.W], "counts": R.to_string(counts)})
+            keep.append(int(i))
+        return segs, keep, scores
 
     def __call__(self, image, boxes, keypoints):
         self.load(image, boxes, keypoints)
@@ -216,6 +285,9 @@ def parse_args(argv=None):
                              "bare state_dict; default: the model's own initialisation")
     parser.add_argument("--max-instances", type=int, default=16)
     parser.add_argument("--iou", type=float, default=0.5, help="mask-NMS IoU threshold")
+    parser.add_argument("--format", choices=("png", "coco"), default="png",
+                        help="png: one PNG per kept instance; coco: COCO RLE results "
+                             "(per-image JSON + results.json), no PNGs")
     return parser.parse_args(argv)
 
 
@@ -251,6 +323,7 @@ def main(argv=None):
     args = parse_args(argv)
     os.makedirs(args.output_dir, exist_ok=True)
     model = load_model(args.checkpoint)
+    coco = args.format == "coco"
     engines = {}
     for filepath in list_images(args.test_image_dir):
         dirname, basename, ext = path_decompose(filepath)
@@ -271,15 +344,27 @@ def main(argv=None):
         cap = min(cap, NMS_MAX) if len(boxes) > args.max_instances else cap
         eng = engines.get((H, W, cap))
         if eng is None:
-            eng = engines[(H, W, cap)] = InstanceSegmenter(model, (H, W), cap, args.iou)
+            eng = engines[(H, W, cap)] = InstanceSegmenter(model, (H, W), cap, args.iou,
+                                                           rle=coco)
         res = {"image": os.path.basename(filepath), "instances": len(boxes), "keep": [],
                "scores": []}
+        if coco:
+            res["segmentation"], res["bbox"] = [], []
         if len(boxes) > eng.K:
             print(f"warning: {basename}: {len(boxes)} instances > {eng.K}: mask-NMS runs per "
                   f"chunk of {eng.K}")
             res["nms"] = f"per chunk of {eng.K}"
         if len(boxes):
             for b0 in range(0, len(boxes), eng.K):
+                if coco:
+                    eng.load(img, boxes[b0:b0 + eng.K], kps[b0:b0 + eng.K])
+                    eng.run()
+                    segs, keep, scores = eng.result_rle()
+                    res["keep"] += [b0 + i for i in keep]
+                    res["scores"] += [float(s) for s in scores]
+                    res["segmentation"] += segs
+                    res["bbox"] += [R.to_bbox(R.from_string(sg["counts"]), H, W) for sg in segs]
+                    continue
                 masks, keep, scores = eng(img, boxes[b0:b0 + eng.K], kps[b0:b0 + eng.K])
                 odir = os.path.join(args.output_dir, basename)
                 os.makedirs(odir, exist_ok=True)
@@ -290,6 +375,8 @@ def main(argv=None):
                 res["scores"] += [float(s) for s in scores]
         with open(out_json, "w") as f:
             json.dump(res, f)
+    if coco:
+        R.write_results(args.output_dir)
     return 0
 
 

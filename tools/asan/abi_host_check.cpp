@@ -56,6 +56,21 @@ int main() {
     g.groups = 1;
     EXPECT(isg_conv_wgrad_rep(&g, nullptr, nullptr, nullptr, nullptr, 0, 4, nullptr) == ISG_ERR_INVALID);
     EXPECT(isg_mask_nms_workspace(16, 1024, 1024) > 0);
+    EXPECT(isg_mask_rle_workspace(16, 1024, 1024) > 0);
+    {   // isg_mask_rle rejects these before any HIP call
+        uint8_t px[16] = {};
+        int64_t off[3] = {};
+        uint32_t wk[64] = {};
+        EXPECT(isg_mask_rle(px, 1, 65536, 32768, nullptr, nullptr, 1, nullptr, 0, off, wk,
+                            nullptr) == ISG_ERR_INVALID);  // H*W == 2^31
+        EXPECT(std::strstr(isg_last_error(), "2^31") != nullptr);
+        EXPECT(isg_mask_rle(px, 1, 4, 4, nullptr, nullptr, 2, nullptr, 0, off, wk, nullptr) ==
+               ISG_ERR_INVALID);  // max_sel > K with sel == NULL
+        EXPECT(isg_mask_rle(px, 1, 4, 4, nullptr, nullptr, 1, nullptr, 8, off, wk, nullptr) ==
+               ISG_ERR_INVALID);  // runs == NULL with runs_cap > 0
+        EXPECT(isg_mask_rle(px, 1, 4, 4, nullptr, nullptr, 1, nullptr, 0, nullptr, wk, nullptr) ==
+               ISG_ERR_INVALID);  // NULL offsets
+    }
 
     // executor: a malformed record size, an unknown kind, then well-formed records whose
     // launches fail without a device (fix-ups and the side-stream batching run first)
