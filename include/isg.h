@@ -449,6 +449,49 @@ int32_t isg_keypoint_heatmaps(const double* keypoints, int32_t K, int32_t nparts
                               int32_t W, double sigma, double threshold, float* out,
                               isg_stream_t stream);
 
+/* ---- training batches (csrc/train_crop.hip) -------------------------------- */
+
+/* One sample of a training batch inside the packed uint8 arena: its image (H x W x 3, HWC)
+ * at byte img_off, its instance mask (H x W) at byte mask_off, and valid = (x0,y0,x1,y1),
+ * the rectangle the reference's centring translation keeps in the frame (data.py
+ * centring_valid). Offsets need no alignment: the kernels read bytes, and dwords only at
+ * addresses they have aligned themselves. */
+typedef struct {
+    int64_t img_off, mask_off;
+    int32_t H, W;
+    int32_t valid[4];
+} isg_train_sample;
+
+#define ISG_TRAIN_PARTS 17 /* keypoints per sample (data.py ORDER_PART_NAMES) */
+#define ISG_TRAIN_PAD 16   /* the window is the mask box +/- this (train_instance.py:166) */
+
+/* The loader's crop on the GPU for the first n of B samples (the CPU statement is
+ * data.py InstanceCommonDataset.__getitem__ / instance_window, bit for bit):
+ *   stage A  the exclusive-max box of the non-zero mask pixels, over the whole mask and over
+ *            the mask inside valid, reduced in the wave and the workgroup, one slot of work
+ *            per workgroup, the slots reduced by stage B (a second tiny pass: no atomics);
+ *            the window is the clipped box if there is one, else the whole-mask box, else
+ *            (0,0,W,H), then +/- ISG_TRAIN_PAD. It never leaves the device.
+ *   stage B  that window of the image resampled to x[b][3][S][S] = (q/255 - 0.5)/0.5 and of
+ *            the mask to mask[b][1][S][S] = q/255 by isg_instance_crop's arithmetic (q the
+ *            uint8 rounded half up; coordinates clamped into the window; 0 outside valid);
+ *            kp_out[b][j] = ((x - wx0) * S / (wx1 - wx0), same in y, visible > 0 ? 1 : 0) in
+ *            double for every part; windows[b] = (x0,y0,x1,y1).
+ * samples is HOST memory (n entries, passed to the kernels by value, ISG_LIST_CHUNK/2 a
+ * launch); arena, keypoints [B][17][3], work and the outputs are device memory. Rows
+ * n .. B-1 of every output are not written. 16-byte stores are used when S % 4 == 0 and x
+ * and mask are 16-byte aligned, 4-byte stores otherwise. Every word of work that is read was
+ * written earlier in the same call (nothing depends on an earlier call, nothing needs
+ * clearing); isg_train_crop_workspace(B) bytes (2 KiB a sample), caller-owned.
+ * Refused with ISG_ERR_INVALID before any HIP call: a NULL pointer, S <= 0, n < 0 or n > B,
+ * a sample with H or W <= 0, with 3*H*W >= 2^31, or reaching outside [0, arena_bytes).
+ * n == 0: nothing is launched, returns 0. */
+int64_t isg_train_crop_workspace(int32_t B);
+int32_t isg_train_crop(const uint8_t* arena, int64_t arena_bytes, const isg_train_sample* samples,
+                       const double* keypoints, int32_t n, int32_t B, int32_t S, void* work,
+                       float* x, float* mask, double* kp_out, int32_t* windows,
+                       isg_stream_t stream);
+
 /* ---- keypoint stem ------------------------------------ */
 
 /* The stem of Segment(20) (init_head_s4, segment.py:19-31, on cat(image, heatmaps),
@@ -571,8 +614,8 @@ int32_t isg_exec_ms2(const void* ops, int32_t nops, void* const* table, isg_stre
 /* sizeof() of the ABI structs and executor records (0 vtensor, 1 sinks, 2 conv record,
  * 3 wgrad record, 4 pool record, 5 tail, 6 tail_grad, 7 bn_update, 8 grad_final,
  * 9 bce record, 10 conv_geom, 11 bn, 12 vseg, 13 sink, 14 sum_rep record, 15 kp_stem,
- * 16 mask_head, 17 stamp record, 18 depthwise-backward record, 19 step tail) so
- * bindings can verify layouts. */
+ * 16 mask_head, 17 stamp record, 18 depthwise-backward record, 19 step tail,
+ * 20 train sample) so bindings can verify layouts. */
 int32_t isg_record_size(int32_t which);
 
 const char* isg_last_error(void);

@@ -20,7 +20,7 @@ SINK_STORE, SINK_ACCUM, SINK_ACTBWD, SINK_NONE = 0, 1, 2, 3
 MAX_SEGS = 3
 LIST_CHUNK = 32
 STAT_REP = int(os.environ.get("ISG_STAT_REP", "4"))  # accumulator replicas (isg.h ISG_STAT_REP)
-ABI_VERSION = 12
+ABI_VERSION = 13
 WREP = int(os.environ.get("ISG_WREP", "16"))  # weight-gradient replicas (isg.h ISG_WREP)
 
 
@@ -170,6 +170,11 @@ class StepIncRec(Structure):
     _fields_ = [("step", c_void_p)]
 
 
+class TrainSample(Structure):  # isg.h isg_train_sample (host memory, passed by value)
+    _fields_ = [("img_off", c_int64), ("mask_off", c_int64), ("H", c_int32), ("W", c_int32),
+                ("valid", c_int32 * 4)]
+
+
 OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_CONVT_FWD = 1, 2, 3, 4
 OP_MAXPOOL_FWD, OP_MAXPOOL_BWD, OP_TAIL_FWD, OP_TAIL_BWD = 5, 6, 7, 8
 OP_BN_UPDATE, OP_GRAD_FINAL, OP_BCE, OP_MEMSET = 9, 10, 11, 12
@@ -184,7 +189,7 @@ OP_STEP_TAIL, OP_STEP_INC = 24, 25
 _RECORD_CHECK = [(0, VTensor), (1, Sinks), (2, ConvRec), (3, WgradRec), (4, PoolRec), (5, Tail),
                  (6, TailGrad), (7, BnUpdate), (8, GradFinal), (9, BceRec), (10, Geom), (11, Bn),
                  (12, VSeg), (13, Sink), (14, SumRepRec), (15, KpStem), (16, MaskHead),
-                 (17, StampRec), (18, DwBwdRec), (19, StepTail)]
+                 (17, StampRec), (18, DwBwdRec), (19, StepTail), (20, TrainSample)]
 
 # exported symbol -> (restype, argtypes)
 SIGNATURES = {
@@ -230,6 +235,10 @@ SIGNATURES = {
                                c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "isg_instance_crop": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                     c_int32, c_void_p, c_void_p]),
+    "isg_train_crop_workspace": (c_int64, [c_int32]),
+    "isg_train_crop": (c_int32, [c_void_p, c_int64, POINTER(TrainSample), c_void_p, c_int32,
+                                 c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
     "isg_keypoint_heatmaps": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_double,
                                         c_double, c_void_p, c_void_p]),
     "isg_kp_stem_fwd": (c_int32, [POINTER(KpStem), c_void_p]),

@@ -107,7 +107,7 @@ static isg_vtensor resolve_y(const isg_vtensor* v) { return isg_resolve_y(v); } 
 extern "C" {
 
 const char* isg_last_error(void) { return g_last_error.c_str(); }
-int32_t isg_abi_version(void) { return 12; }  // 12: isg_mask_rle (mask_rle.hip)
+int32_t isg_abi_version(void) { return 13; }  // 13: isg_train_crop (train_crop.hip)
 int32_t isg_stat_replicas(void) { return ISG_STAT_REP; }
 
 int32_t isg_conv_fwd(const isg_conv_geom* g, const isg_vtensor* x_, const float* w,
@@ -693,6 +693,7 @@ int32_t isg_record_size(int32_t which) {
         case 17: return (int32_t)sizeof(StampRec);
         case 18: return (int32_t)sizeof(DwBwdRec);
         case 19: return (int32_t)sizeof(isg_step_tail_args);
+        case 20: return (int32_t)sizeof(isg_train_sample);
         default: return -1;
     }
 }

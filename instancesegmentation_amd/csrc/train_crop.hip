@@ -1,0 +1,299 @@
+// Training batches prepared on the GPU (isg_train_crop, isg.h): what the loader's
+// InstanceCommonDataset.__getitem__ (data.py) does per sample after decoding, for B samples
+// that each come from an image of their own size, packed with their masks into one uint8
+// arena.
+//
+//   train_box_kernel   stage A. Per sample the box of the non-zero mask pixels, twice in one
+//                      pass: over the whole mask and over the mask inside `valid` (the
+//                      centring translation's frame). The mask is read as dwords at
+//                      addresses aligned here (its offset in the arena is arbitrary), the
+//                      first and last partial dword as bytes, four loads in flight per
+//                      thread. Each bound is kept in a form that only grows (W - min x,
+//                      H - min y, max x + 1, max y + 1; 0 = nothing seen), so every
+//                      reduction is a max: in the lane, across the wave by shuffles, across
+//                      the workgroup through LDS. Every workgroup then stores its eight
+//                      numbers in its own slot of the workspace and stage B takes the max
+//                      over a sample's slots: no atomics (a first version sent one integer
+//                      atomic max per wave and bound to a sample's single 32-byte record
+//                      and spent 82 us there for eight 640 x 480 masks) and nothing to clear,
+//                      since every slot that is read was written by the same call.
+//   train_crop_kernel  stage B. Derives the window from those numbers (data.py
+//                      instance_window: the clipped box, else the whole-mask box, else the
+//                      image, then +/- 16) and resamples it to S x S: crop_kernel's
+//                      arithmetic (infer_ops.hip; every float op one IEEE op in the oracle's
+//                      order, contraction off), the coordinates and weights computed once per
+//                      output pixel for the three image planes and the mask plane. V
+//                      consecutive u per lane, one 16-byte store per plane when V == 4.
+//                      Workgroup 0 of a sample also writes its window and projects its 17
+//                      keypoints through it in double.
+//
+// Sample descriptors are host memory and reach the kernels by value, kChunk to a launch.
+// A tap is loaded only through an index that was made valid first (offset 0 when the tap
+// lies outside valid), so no address outside the sample's image or mask is ever formed
+// into a load.
+#include "common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kChunk = ISG_LIST_CHUNK / 2;  // 16 samples x 40 B of kernel arguments
+constexpr int kWaves = kThreads / 64;
+constexpr int kBoxBlocksMax = 64;           // workgroups (and workspace slots) per sample of stage A
+constexpr int kBoxU = 4;                    // dword loads of a thread in flight together
+constexpr int kBoxGroups = 2 * kBoxU;       // dwords per thread that size stage A's grid
+
+struct TrainChunk {
+    isg_train_sample s[kChunk];
+};
+
+typedef const uint32_t __attribute__((address_space(1)))* gcu32_p;
+
+// ---- stage A -----------------------------------------------------------------------
+// dword g of the mask's aligned image: pixels p0 .. p0+3, p0 = 4*g - head; bytes outside the
+// mask (and every g >= ngroups) read as 0 and are never loaded
+ISG_DEV uint32_t box_load(const uint8_t* m, int hw, int head, int g, int ngroups) {
+    if (g >= ngroups) return 0u;
+    const int p0 = 4 * g - head;
+    if (p0 >= 0 && p0 + 4 <= hw) return *(gcu32_p)(m + p0);  // 4-byte aligned, inside the mask
+    uint32_t v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (p0 + b >= 0 && p0 + b < hw) v |= (uint32_t)m[p0 + b] << (8 * b);
+    return v;
+}
+
+__global__ __launch_bounds__(kThreads) void train_box_kernel(const uint8_t* __restrict__ arena,
+                                                              TrainChunk ch, int base,
+                                                              int32_t* __restrict__ work) {
+    __shared__ int s_a[kWaves][8];
+    const int k = blockIdx.y;
+    const int H = ch.s[k].H, W = ch.s[k].W;
+    const int vx0 = max(ch.s[k].valid[0], 0), vy0 = max(ch.s[k].valid[1], 0);
+    const int vx1 = min(ch.s[k].valid[2], W), vy1 = min(ch.s[k].valid[3], H);
+    const uint8_t* m = arena + ch.s[k].mask_off;
+    const int hw = H * W;                          // 3*H*W < 2^31 (checked by the caller)
+    const int head = (int)((uintptr_t)m & 3);      // bytes of the first dword before the mask
+    const int ngroups = (hw + head + 3) >> 2;
+    const int stride = gridDim.x * kThreads;
+    int a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int g0 = blockIdx.x * kThreads + threadIdx.x; g0 < ngroups; g0 += kBoxU * stride) {
+        uint32_t v[kBoxU];
+#pragma unroll
+        for (int u = 0; u < kBoxU; ++u) v[u] = box_load(m, hw, head, g0 + u * stride, ngroups);
+#pragma unroll
+        for (int u = 0; u < kBoxU; ++u) {
+            if (v[u] == 0) continue;
+            const int p0 = 4 * (g0 + u * stride) - head;  // pixel of the dword's byte 0
+            const int pb = max(p0, 0);
+            int y = pb / W, x = pb - y * W;        // the first byte that belongs to the mask
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                if (p0 + b < pb) continue;
+                if ((v[u] >> (8 * b)) & 0xffu) {   // non-zero is the rule (data.py mask_box)
+                    a[0] = max(a[0], W - x); a[1] = max(a[1], H - y);
+                    a[2] = max(a[2], x + 1); a[3] = max(a[3], y + 1);
+                    if (x >= vx0 && x < vx1 && y >= vy0 && y < vy1) {
+                        a[4] = max(a[4], W - x); a[5] = max(a[5], H - y);
+                        a[6] = max(a[6], x + 1); a[7] = max(a[7], y + 1);
+                    }
+                }
+                if (++x == W) { x = 0; ++y; }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) a[i] = max(a[i], __shfl_xor(a[i], o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s_a[threadIdx.x >> 6][i] = a[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {  // this workgroup's slot, written whether or not it saw a pixel
+        int r = 0;
+#pragma unroll
+        for (int wv = 0; wv < kWaves; ++wv) r = max(r, s_a[wv][threadIdx.x]);
+        work[((int64_t)(base + k) * kBoxBlocksMax + blockIdx.x) * 8 + threadIdx.x] = r;
+    }
+}
+
+// ---- stage B -----------------------------------------------------------------------
+struct Tap {        // one output coordinate along one axis
+    float a, b;     // weights of the far and the near tap (a = frac, b = 1 - a)
+    int c0, c1;     // tap coordinates clamped into the window
+    bool o0, o1;    // tap inside valid (and therefore inside the image)
+};
+
+// crop_kernel's coordinate arithmetic (infer_ops.hip), operation for operation
+ISG_DEV Tap make_tap(int i, float scale, int lo, int hi, int vlo, int vhi) {
+#pragma clang fp contract(off)
+    Tap t;
+    const float f = (((float)i + 0.5f) * scale - 0.5f) + (float)lo;
+    const float fl = floorf(f);
+    t.a = f - fl;
+    t.b = 1.f - t.a;
+    const int ii = (int)fl;
+    t.c0 = min(max(ii, lo), hi - 1);
+    t.c1 = min(max(ii + 1, lo), hi - 1);
+    t.o0 = t.c0 >= vlo && t.c0 < vhi;
+    t.o1 = t.c1 >= vlo && t.c1 < vhi;
+    return t;
+}
+
+ISG_DEV int quantise(float by, float top, float ay, float bot) {
+#pragma clang fp contract(off)
+    const float val = (by * top) + (ay * bot);
+    const int q = (int)(val + 0.5f);
+    return q < 0 ? 0 : (q > 255 ? 255 : q);
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void train_crop_kernel(
+    const uint8_t* __restrict__ arena, TrainChunk ch, int base, const int32_t* __restrict__ work,
+    int nbox, const double* __restrict__ kp, int S, float* __restrict__ xo, float* __restrict__ mo,
+    double* __restrict__ kpo, int32_t* __restrict__ wino) {
+#pragma clang fp contract(off)
+    __shared__ int s_w[kWaves][8];
+    const int k = blockIdx.y, b = base + k;
+    const int H = ch.s[k].H, W = ch.s[k].W;
+    {   // the max over the nbox slots stage A wrote for this sample (nbox <= 64: two a thread)
+        const int i = threadIdx.x & 7, j = threadIdx.x >> 3;
+        const int32_t* slot = work + (int64_t)b * kBoxBlocksMax * 8 + i;
+        int r = max(j < nbox ? slot[j * 8] : 0, j + 32 < nbox ? slot[(j + 32) * 8] : 0);
+#pragma unroll
+        for (int o = 32; o >= 8; o >>= 1) r = max(r, __shfl_xor(r, o, 64));
+        if ((threadIdx.x & 63) < 8) s_w[threadIdx.x >> 6][i] = r;
+    }
+    __syncthreads();
+    int w[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        w[i] = 0;
+#pragma unroll
+        for (int wv = 0; wv < kWaves; ++wv) w[i] = max(w[i], s_w[wv][i]);
+    }
+    int x0 = 0, y0 = 0, x1 = W, y1 = H;  // no mask pixel at all (train_instance.py:163-164)
+    if (w[6] > 0) {
+        x0 = W - w[4]; y0 = H - w[5]; x1 = w[6]; y1 = w[7];
+    } else if (w[2] > 0) {  // every mask pixel was pushed out of the frame
+        x0 = W - w[0]; y0 = H - w[1]; x1 = w[2]; y1 = w[3];
+    }
+    x0 -= ISG_TRAIN_PAD; y0 -= ISG_TRAIN_PAD; x1 += ISG_TRAIN_PAD; y1 += ISG_TRAIN_PAD;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < 4)
+            wino[4 * b + threadIdx.x] = threadIdx.x == 0 ? x0 : threadIdx.x == 1 ? y0
+                                        : threadIdx.x == 2 ? x1 : y1;
+        if (threadIdx.x < ISG_TRAIN_PARTS) {  // numpy's float64 arithmetic, one op at a time
+            const int64_t j = ((int64_t)b * ISG_TRAIN_PARTS + threadIdx.x) * 3;
+            kpo[j] = ((kp[j] - (double)x0) * (double)S) / (double)(x1 - x0);
+            kpo[j + 1] = ((kp[j + 1] - (double)y0) * (double)S) / (double)(y1 - y0);
+            kpo[j + 2] = kp[j + 2] > 0.0 ? 1.0 : 0.0;
+        }
+    }
+    const int64_t ss = (int64_t)S * S;
+    const int64_t o = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * V;
+    if (o >= ss) return;
+    const int v = (int)(o / S), u0 = (int)(o - (int64_t)v * S);  // V == 4: S % 4 == 0, one row
+    const int vx0 = max(ch.s[k].valid[0], 0), vy0 = max(ch.s[k].valid[1], 0);
+    const int vx1 = min(ch.s[k].valid[2], W), vy1 = min(ch.s[k].valid[3], H);
+    const uint8_t* img = arena + ch.s[k].img_off;
+    const uint8_t* msk = arena + ch.s[k].mask_off;
+    const float sx = (float)(x1 - x0) / (float)S;
+    const float sy = (float)(y1 - y0) / (float)S;
+    const Tap ty = make_tap(v, sy, y0, y1, vy0, vy1);
+    float r[4][V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const Tap tx = make_tap(u0 + j, sx, x0, x1, vx0, vx1);
+        const bool k00 = ty.o0 && tx.o0, k01 = ty.o0 && tx.o1;
+        const bool k10 = ty.o1 && tx.o0, k11 = ty.o1 && tx.o1;
+        // pixel index of each tap, 0 (always inside the sample) where the tap is not read
+        const int i00 = k00 ? ty.c0 * W + tx.c0 : 0, i01 = k01 ? ty.c0 * W + tx.c1 : 0;
+        const int i10 = k10 ? ty.c1 * W + tx.c0 : 0, i11 = k11 ? ty.c1 * W + tx.c1 : 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint8_t* p = c < 3 ? img + c : msk;
+            const int st = c < 3 ? 3 : 1;
+            const uint8_t q00 = p[i00 * st], q01 = p[i01 * st], q10 = p[i10 * st], q11 = p[i11 * st];
+            const float s00 = k00 ? (float)q00 : 0.f, s01 = k01 ? (float)q01 : 0.f;
+            const float s10 = k10 ? (float)q10 : 0.f, s11 = k11 ? (float)q11 : 0.f;
+            const float top = (tx.b * s00) + (tx.a * s01);
+            const float bot = (tx.b * s10) + (tx.a * s11);
+            const int q = quantise(ty.b, top, ty.a, bot);
+            r[c][j] = c < 3 ? ((float)q / 255.f - 0.5f) / 0.5f : (float)q / 255.f;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float* dst = c < 3 ? xo + ((int64_t)b * 3 + c) * ss : mo + (int64_t)b * ss;
+        if (V == 4) {
+            gst4(dst, o, f32x4{r[c][0], r[c][1], r[c][2], r[c][3]});
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) gst(dst, o + j, r[c][j]);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t isg_train_crop_workspace(int32_t B) {
+    return B > 0 ? (int64_t)B * kBoxBlocksMax * 8 * (int64_t)sizeof(int32_t) : 0;
+}
+
+int32_t isg_train_crop(const uint8_t* arena, int64_t arena_bytes, const isg_train_sample* samples,
+                       const double* keypoints, int32_t n, int32_t B, int32_t S, void* work,
+                       float* x, float* mask, double* kp_out, int32_t* windows, isg_stream_t st) {
+    if (!arena || !samples || !keypoints || !work || !x || !mask || !kp_out || !windows)
+        return isg_set_error(ISG_ERR_INVALID, "train_crop: NULL pointer");
+    if (S <= 0 || n < 0 || n > B)
+        return isg_set_error(ISG_ERR_INVALID, "train_crop: bad sizes S=%d n=%d B=%d", S, n, B);
+    int64_t max_hw = 0;
+    for (int i = 0; i < n; ++i) {
+        const isg_train_sample& s = samples[i];
+        if (s.H <= 0 || s.W <= 0)
+            return isg_set_error(ISG_ERR_INVALID, "train_crop: sample %d is %d x %d", i, s.H, s.W);
+        const int64_t hw = (int64_t)s.H * s.W;
+        if (3 * hw >= ((int64_t)1 << 31))
+            return isg_set_error(ISG_ERR_INVALID, "train_crop: sample %d: 3*H*W = %lld needs < 2^31",
+                                 i, (long long)(3 * hw));
+        if (s.img_off < 0 || s.mask_off < 0 || s.img_off > arena_bytes - 3 * hw ||
+            s.mask_off > arena_bytes - hw)
+            return isg_set_error(ISG_ERR_INVALID,
+                                 "train_crop: sample %d (image at %lld, mask at %lld, %d x %d) "
+                                 "reaches outside the arena of %lld bytes", i, (long long)s.img_off,
+                                 (long long)s.mask_off, s.H, s.W, (long long)arena_bytes);
+        max_hw = hw > max_hw ? hw : max_hw;
+    }
+    if (n == 0) return ISG_OK;
+    const int64_t ss = (int64_t)S * S;
+    const bool wide = S % 4 == 0 && (((uintptr_t)x | (uintptr_t)mask) & 15) == 0;
+    const int64_t crop_blocks = (ss + (int64_t)kThreads * (wide ? 4 : 1) - 1) /
+                                ((int64_t)kThreads * (wide ? 4 : 1));
+    if (crop_blocks > 0x7fffffff)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "train_crop: %lld workgroups", (long long)crop_blocks);
+    const int64_t per_block = (int64_t)kThreads * kBoxGroups * 4;  // mask bytes per workgroup
+    int box_blocks = (int)((max_hw + per_block - 1) / per_block);
+    box_blocks = box_blocks < 1 ? 1 : (box_blocks > kBoxBlocksMax ? kBoxBlocksMax : box_blocks);
+    for (int base = 0; base < n; base += kChunk) {
+        const int cnt = n - base < kChunk ? n - base : kChunk;
+        TrainChunk ch;
+        for (int i = 0; i < kChunk; ++i) ch.s[i] = samples[base + (i < cnt ? i : 0)];
+        hipLaunchKernelGGL(train_box_kernel, dim3((unsigned)box_blocks, (unsigned)cnt),
+                           dim3(kThreads), 0, st, arena, ch, base, (int32_t*)work);
+        const dim3 grid((unsigned)crop_blocks, (unsigned)cnt);
+        if (wide)
+            hipLaunchKernelGGL(train_crop_kernel<4>, grid, dim3(kThreads), 0, st, arena, ch, base,
+                               (const int32_t*)work, box_blocks, keypoints, S, x, mask, kp_out, windows);
+        else
+            hipLaunchKernelGGL(train_crop_kernel<1>, grid, dim3(kThreads), 0, st, arena, ch, base,
+                               (const int32_t*)work, box_blocks, keypoints, S, x, mask, kp_out, windows);
+    }
+    return isg_check_launch("train_crop kernels");
+}
+
+}  // extern "C"

@@ -212,6 +212,27 @@ def crop_resample(img, window, valid, size):
     return np.clip((val + f32(0.5)).astype(np.int64), 0, 255).astype(np.uint8)
 
 
+def instance_window(mask, valid, pad=16):
+    """The crop window (x0, y0, x1, y1) of one sample (train_instance.py:148-166): the box of
+    the mask's non-zero pixels that the centring translation leaves in the frame (`valid`,
+    clamped to the image), else, when it pushed all of them out, the box of the whole mask,
+    else the whole image (:163-164); then +/- pad. The CPU statement of stage A of
+    isg_train_crop (csrc/train_crop.hip)."""
+    mask = np.asarray(mask)
+    ih, iw = mask.shape[:2]
+    ib = mask_box(mask)
+    if ib is None:
+        ib = (0, 0, iw, ih)
+    vx0, vy0 = max(int(valid[0]), 0), max(int(valid[1]), 0)
+    vx1, vy1 = min(int(valid[2]), iw), min(int(valid[3]), ih)
+    # a mask pixel pushed out of the frame by the translation is gone before mask2box
+    m = np.zeros_like(mask)
+    if vx1 > vx0 and vy1 > vy0:
+        m[vy0:vy1, vx0:vx1] = mask[vy0:vy1, vx0:vx1]
+    ib = mask_box(m) or ib
+    return ib[0] - pad, ib[1] - pad, ib[2] + pad, ib[3] + pad
+
+
 class InstanceCommonDataset(torch.utils.data.Dataset):
     """train_instance.py:71-216 on the common-dataset layout, without imgaug/ymlib.
 
@@ -221,10 +242,12 @@ class InstanceCommonDataset(torch.utils.data.Dataset):
     from the keypoints, :200-202, and drops them — Segment(20) needs them). The
     augmentation is the reference's active one (both branches, :148-196; the random ones
     are commented out there): translate the box centre to the image centre, crop/pad to
-    the instance mask's box +/- 16 px, resize to 480x480 — one resampling, the same
-    contract as the GPU crop kernel."""
+    the instance mask's box +/- 16 px (instance_window), resize to 480x480 — one
+    resampling, the same contract as the GPU crop kernel. With raw=True the sample is only
+    decoded and a batch of them is cropped on the GPU (raw_collate_fn, gpu_batch.py)."""
 
-    def __init__(self, dataset_dir, test: bool = False, with_heatmaps: bool = True) -> None:
+    def __init__(self, dataset_dir, test: bool = False, with_heatmaps: bool = True,
+                 raw: bool = False) -> None:
         super().__init__()
         import glob
         import json
@@ -234,6 +257,10 @@ class InstanceCommonDataset(torch.utils.data.Dataset):
         # which the GPU stem synthesises the same heatmaps (kp_stem.hip) — the dense
         # 17 x 480 x 480 maps are then neither computed on the host nor copied to HBM
         self.with_heatmaps = with_heatmaps
+        # True: __getitem__ only decodes — (image uint8 [H,W,3], mask uint8 [H,W], valid
+        # int64 [4], keypoints float64 [17,3] in IMAGE coordinates); the window, the
+        # resampling and the keypoint projection are then the GPU's (gpu_batch.GpuBatcher)
+        self.raw = raw
         self.out_size = (480, 480)
         self.root = dataset_dir
         self.results = []
@@ -259,19 +286,14 @@ class InstanceCommonDataset(torch.utils.data.Dataset):
         ih, iw = image.shape[:2]
         box = [float(v) for v in ckey(r, "box")[:4]]
         valid = centring_valid(box, ih, iw)
-        ib = mask_box(mask)
-        if ib is None:
-            ib = (0, 0, iw, ih)                               # train_instance.py:163-164
-        # a mask pixel pushed out of the frame by the translation is gone before mask2box
-        m = np.zeros_like(mask)
-        m[valid[1]:valid[3], valid[0]:valid[2]] = mask[valid[1]:valid[3], valid[0]:valid[2]]
-        ib = mask_box(m) or ib
-        pad = 16
-        win = (ib[0] - pad, ib[1] - pad, ib[2] + pad, ib[3] + pad)
+        kp = _keypoint_table(ckey(r, "body_keypoint", {}) or {})
+        if self.raw:
+            return (np.ascontiguousarray(image), np.ascontiguousarray(mask),
+                    np.asarray(valid, np.int64), kp)
+        win = instance_window(mask, valid, pad=16)
         S = self.out_size[0]
         img_c = crop_resample(image, win, valid, S)
         mask_c = crop_resample(mask, win, valid, S)[:, :, 0]
-        kp = _keypoint_table(ckey(r, "body_keypoint", {}) or {})
         kp[:, 0] = (kp[:, 0] - win[0]) * S / (win[2] - win[0])
         kp[:, 1] = (kp[:, 1] - win[1]) * S / (win[3] - win[1])
         kp[:, 2] = (kp[:, 2] > 0).astype(np.float64)
@@ -294,3 +316,32 @@ def collate_fn(batch):
         return samples
 
     return [deal(list(samples)) for samples in zip(*batch)]
+
+
+RAW_DESC_COLS = ("img_off", "mask_off", "H", "W", "vx0", "vy0", "vx1", "vy1")
+
+
+def raw_collate_fn(batch):
+    """Pack raw samples (InstanceCommonDataset(raw=True)) for one upload: (arena, desc,
+    keypoints) = a uint8 tensor holding every image (HWC) and mask (HW) back to back with no
+    padding (the kernels take any byte offset), an int64 [n, 8] table of RAW_DESC_COLS per
+    sample (`valid` clipped to int32's range), and the keypoints float64 [n, 17, 3] in image
+    coordinates."""
+    n = len(batch)
+    desc = np.zeros((n, len(RAW_DESC_COLS)), np.int64)
+    total = 0
+    for i, (image, mask, valid, _) in enumerate(batch):
+        h, w = mask.shape
+        if image.shape != (h, w, 3) or image.dtype != np.uint8 or mask.dtype != np.uint8:
+            raise ValueError(f"raw sample {i}: image {image.shape} {image.dtype}, "
+                             f"mask {mask.shape} {mask.dtype}")
+        desc[i, :4] = (total, total + 3 * h * w, h, w)
+        desc[i, 4:] = np.clip(np.asarray(valid, np.int64), -2 ** 31, 2 ** 31 - 1)
+        total += 4 * h * w
+    arena = np.empty(total, np.uint8)
+    for i, (image, mask, _, _) in enumerate(batch):
+        h, w = int(desc[i, 2]), int(desc[i, 3])
+        arena[desc[i, 0]:desc[i, 0] + 3 * h * w] = image.reshape(-1)
+        arena[desc[i, 1]:desc[i, 1] + h * w] = mask.reshape(-1)
+    kp = np.stack([np.asarray(s[3], np.float64) for s in batch]) if n else np.zeros((0, N_PARTS, 3))
+    return torch.from_numpy(arena), torch.from_numpy(desc), torch.from_numpy(kp)

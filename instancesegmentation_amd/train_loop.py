@@ -18,6 +18,7 @@ Differences from the reference, all deliberate:
 
     python -m instancesegmentation_amd.train_loop --train-dataset-dir D --val-dataset-dir V \\
         --checkpoint-dir C [--epoch 30 --batch-size 8 --val-iter 120 --show-iter 20 ...]
+        [--gpu-crop]    the loader's crop on the GPU: the workers only decode (gpu_batch.py)
 """
 import argparse
 import os
@@ -26,7 +27,7 @@ import subprocess
 import numpy as np
 import torch
 
-from .data import InstanceCommonDataset, collate_fn
+from .data import InstanceCommonDataset, collate_fn, raw_collate_fn
 
 
 def tensor2mask(tensor):
@@ -106,6 +107,8 @@ def parse_args(argv=None):
     p.add_argument("--batch-size", type=int, default=8)
     p.add_argument("--cpu-num", type=int, default=2)
     p.add_argument("--max-steps", type=int, default=0, help="stop after this many steps (0: off)")
+    p.add_argument("--gpu-crop", action="store_true",
+                   help="workers only decode; mask box, crop and keypoints on the GPU (gpu_batch.py)")
     return p.parse_args(argv)
 
 
@@ -120,6 +123,21 @@ def _batches(loader, device):
                mask_ts.to(device, non_blocking=True), results)
 
 
+def _gpu_batches(loader, batcher, trainer=None):
+    """--gpu-crop: (inputs, mask, raw batch) per batch of a raw loader, cropped by `batcher`.
+    With a trainer the results are written straight into its static input buffers (the batch
+    is full: drop_last) and inputs is None — `trainer.step(None, None)` then copies nothing;
+    without one they are views of the batcher's own buffers, valid until its next batch."""
+    for raw in loader:
+        if trainer is not None:
+            _, _, mask, n = batcher.prepare(raw, trainer.inputs[0], trainer.inputs[1], trainer.target)
+            assert n == batcher.B
+            yield None, mask, raw
+        else:
+            x, kp, mask, _ = batcher.prepare(raw)
+            yield [x, kp], mask, raw
+
+
 def fit(args, device=None, process_group=None):
     """The reference loop (train_instance.py:272-515) on the fused Trainer."""
     import torch.distributed as dist
@@ -129,14 +147,17 @@ def fit(args, device=None, process_group=None):
     device = torch.device(device or "cuda")
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
-    trainset = InstanceCommonDataset(args.train_dataset_dir, with_heatmaps=False)
-    valset = InstanceCommonDataset(args.val_dataset_dir, test=True, with_heatmaps=False)
+    gpu_crop = bool(getattr(args, "gpu_crop", False))
+    collate = raw_collate_fn if gpu_crop else collate_fn
+    trainset = InstanceCommonDataset(args.train_dataset_dir, with_heatmaps=False, raw=gpu_crop)
+    valset = InstanceCommonDataset(args.val_dataset_dir, test=True, with_heatmaps=False,
+                                   raw=gpu_crop)
     sampler = (torch.utils.data.distributed.DistributedSampler(trainset) if world > 1 else None)
     trainloader = torch.utils.data.DataLoader(
         trainset, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
-        num_workers=args.cpu_num, collate_fn=collate_fn, drop_last=True)
+        num_workers=args.cpu_num, collate_fn=collate, drop_last=True)
     valloader = torch.utils.data.DataLoader(valset, batch_size=args.batch_size, shuffle=True,
-                                            num_workers=1, collate_fn=collate_fn)
+                                            num_workers=1, collate_fn=collate)
     S = trainset.out_size[0]
     model = Segment(20)
     trainer = Trainer(model, args.batch_size, [(args.batch_size, 3, S, S),
@@ -156,6 +177,16 @@ def fit(args, device=None, process_group=None):
         load_checkpoint(args.pretrained_path, trainer)
         start_epoch = 0
     trainer.capture()
+    batcher = None
+    if gpu_crop:
+        from .gpu_batch import GpuBatcher
+        batcher = GpuBatcher(args.batch_size, S, device)
+
+    def batches(loader, into=None):
+        if gpu_crop:
+            return _gpu_batches(loader, batcher, into)
+        return _batches(loader, device)
+
     steps = 0
     epoch = start_epoch
     history = []
@@ -164,8 +195,9 @@ def fit(args, device=None, process_group=None):
             sampler.set_epoch(epoch)
         loss_total = []
         restart = False
-        for i0, (xs, mask, results) in enumerate(_batches(trainloader, device)):
-            loss = trainer.step(xs, mask)
+        for i0, (xs, mask, results) in enumerate(batches(trainloader, trainer)):
+            # (--gpu-crop: the batch is already in the trainer's buffers, nothing is copied)
+            loss = trainer.step(xs, mask if xs is not None else None)
             loss_total.append(loss)
             steps += 1
             if i0 % args.show_iter == args.show_iter - 1 and rank == 0:
@@ -177,7 +209,7 @@ def fit(args, device=None, process_group=None):
                 if rank == 0:
                     train_iou = tensors_mean_iou(trainer.probabilities(), mask)
                     val_ious = []
-                    for vxs, vmask, _ in _batches(valloader, device):
+                    for vxs, vmask, _ in batches(valloader):
                         val_ious.append(tensors_mean_iou(trainer.predict(vxs), vmask))
                         break  # the reference validates on one batch (:414-415)
                     val_iou = mean(val_ious) if val_ious else 0.0

@@ -72,6 +72,29 @@ int main() {
                ISG_ERR_INVALID);  // NULL offsets
     }
 
+    EXPECT(isg_train_crop_workspace(8) == 8 * 2048 && isg_train_crop_workspace(0) == 0);
+    {   // isg_train_crop rejects these before any HIP call (the descriptors are host memory)
+        uint8_t px[4 * 6 * 5] = {};
+        double kp[ISG_TRAIN_PARTS * 3] = {}, kpo[ISG_TRAIN_PARTS * 3] = {};
+        int32_t wk[8] = {}, win[4] = {};
+        float x[3 * 4] = {}, m[4] = {};
+        isg_train_sample s{};
+        s.img_off = 0; s.mask_off = 90; s.H = 6; s.W = 5; s.valid[2] = 5; s.valid[3] = 6;
+        const int64_t nb = (int64_t)sizeof(px);
+        EXPECT(isg_train_crop(px, nb, &s, kp, 0, 1, 2, wk, x, m, kpo, win, nullptr) == ISG_OK);  // n == 0
+        EXPECT(isg_train_crop(nullptr, nb, &s, kp, 1, 1, 2, wk, x, m, kpo, win, nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_train_crop(px, nb, nullptr, kp, 1, 1, 2, wk, x, m, kpo, win, nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_train_crop(px, nb, &s, kp, 1, 1, 0, wk, x, m, kpo, win, nullptr) == ISG_ERR_INVALID);  // S
+        EXPECT(isg_train_crop(px, nb, &s, kp, 2, 1, 2, wk, x, m, kpo, win, nullptr) == ISG_ERR_INVALID);  // n > B
+        EXPECT(isg_train_crop(px, nb - 1, &s, kp, 1, 1, 2, wk, x, m, kpo, win, nullptr) == ISG_ERR_INVALID);
+        EXPECT(std::strstr(isg_last_error(), "outside the arena") != nullptr);
+        s.H = 0;
+        EXPECT(isg_train_crop(px, nb, &s, kp, 1, 1, 2, wk, x, m, kpo, win, nullptr) == ISG_ERR_INVALID);
+        s.H = 30000; s.W = 30000;
+        EXPECT(isg_train_crop(px, nb, &s, kp, 1, 1, 2, wk, x, m, kpo, win, nullptr) == ISG_ERR_INVALID);
+        EXPECT(std::strstr(isg_last_error(), "2^31") != nullptr);
+    }
+
     // executor: a malformed record size, an unknown kind, then well-formed records whose
     // launches fail without a device (fix-ups and the side-stream batching run first)
     std::vector<char> blob;
