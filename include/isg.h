@@ -492,6 +492,50 @@ int32_t isg_train_crop(const uint8_t* arena, int64_t arena_bytes, const isg_trai
                        float* x, float* mask, double* kp_out, int32_t* windows,
                        isg_stream_t stream);
 
+/* The augmentation of one sample, drawn by the host (augment.py draw_augment): the kernel takes
+ * parameters, never probabilities. All zero but rot_cos = contrast = mult[] = 1 is the identity. */
+typedef struct {
+    double rot_cos, rot_sin; /* rotation of the output grid about the crop's centre; (1, 0) = none */
+    int32_t jitter[4];       /* each in [-1024, 1024]: side i of the padded window (x0, y0, x1, y1)
+                              * moves by floor(jitter[i] * (box extent / 5) / 1024) pixels */
+    int32_t flip;            /* 0 / 1: mirror the columns, exchange the left and right keypoints */
+    int32_t noise_per_channel; /* 0: one noise value a pixel for the three planes; 1: one each */
+    float contrast;          /* q -> (q - 127) * contrast + 127 */
+    float noise;             /* q -> q + (s - 510) * noise, s the sum of four Philox bytes; 0 = none */
+    float mult[3];           /* q -> q * mult[c] */
+    int32_t pad_;
+} isg_train_aug;
+
+#define ISG_TRAIN_AUG_MAX 65536.0f /* upper bound of contrast, noise and mult[] */
+
+/* isg_train_crop with random geometry and colour in stage B (the CPU statement is augment.py
+ * augment_sample, bit for bit; stage A is isg_train_crop's):
+ *   window   the box before the pad is isg_train_crop's (bx0,by0,bx1,by1); ax = (bx1-bx0)/5,
+ *            ay = (by1-by0)/5; x0 = bx0 - 16 + floor(jitter[0]*ax/1024), x1 = bx1 + 16 +
+ *            floor(jitter[2]*ax/1024), y0 and y1 alike with jitter[1], jitter[3] and ay.
+ *   geometry rot = (1, 0): isg_train_crop's resampling of that window; flip writes column u
+ *            from column S-1-u. Otherwise output (u, v), u un-flipped, samples the crop at
+ *            p = R (u + 0.5 - S/2, v + 0.5 - S/2) + S/2, R = [[cos, -sin], [sin, cos]] in float,
+ *            mapped into the image like an output centre ((p * scale) - 0.5) + lo; bilinear
+ *            taps at floor and floor + 1 without clamping, 0 outside valid and the image.
+ *   colour   on the quantised image planes, each step rounded half up and clamped to 0..255:
+ *            contrast, noise, mult (see the record); then (q/255 - 0.5)/0.5. The noise of output
+ *            pixel i = v*S + u of sample b is Philox4x32-10 with key (seed lo, seed hi) and
+ *            counter (i lo, i hi, o lo, o hi), o = ordinal0 + b; plane c sums the four bytes of
+ *            output word c (noise_per_channel) or word 0.
+ *   keypoints  projected as by isg_train_crop, then (if rotated) R^T applied about (S/2, S/2),
+ *            then (if flipped) x -> S - x and the left/right rows exchanged with visibility.
+ * aug is HOST memory, n records, passed by value with the sample descriptors. Everything
+ * isg_train_crop refuses is refused, and also: aug == NULL, a jitter outside +/-1024,
+ * |cos^2 + sin^2 - 1| > 1e-6, flip or noise_per_channel not 0 / 1, a contrast, noise or mult
+ * that is negative, not finite or above ISG_TRAIN_AUG_MAX. With identity records the outputs
+ * are isg_train_crop's. */
+int32_t isg_train_crop_aug(const uint8_t* arena, int64_t arena_bytes, const isg_train_sample* samples,
+                           const isg_train_aug* aug, uint64_t seed, uint64_t ordinal0,
+                           const double* keypoints, int32_t n, int32_t B, int32_t S, void* work,
+                           float* x, float* mask, double* kp_out, int32_t* windows,
+                           isg_stream_t stream);
+
 /* ---- keypoint stem ------------------------------------ */
 
 /* The stem of Segment(20) (init_head_s4, segment.py:19-31, on cat(image, heatmaps),

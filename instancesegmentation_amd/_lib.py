@@ -7,7 +7,8 @@ already loaded (both carry SONAME libamdhip64.so.7).
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_void_p
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_uint64,
+                    c_void_p)
 
 import torch  # noqa: F401  (load torch's HIP runtime before libisg)
 
@@ -20,7 +21,7 @@ SINK_STORE, SINK_ACCUM, SINK_ACTBWD, SINK_NONE = 0, 1, 2, 3
 MAX_SEGS = 3
 LIST_CHUNK = 32
 STAT_REP = int(os.environ.get("ISG_STAT_REP", "4"))  # accumulator replicas (isg.h ISG_STAT_REP)
-ABI_VERSION = 13
+ABI_VERSION = 14
 WREP = int(os.environ.get("ISG_WREP", "16"))  # weight-gradient replicas (isg.h ISG_WREP)
 
 
@@ -175,6 +176,12 @@ class TrainSample(Structure):  # isg.h isg_train_sample (host memory, passed by 
                 ("valid", c_int32 * 4)]
 
 
+class TrainAug(Structure):  # isg.h isg_train_aug (host memory; augment.AUG_DTYPE is its numpy form)
+    _fields_ = [("rot_cos", c_double), ("rot_sin", c_double), ("jitter", c_int32 * 4),
+                ("flip", c_int32), ("noise_per_channel", c_int32), ("contrast", c_float),
+                ("noise", c_float), ("mult", c_float * 3), ("pad_", c_int32)]
+
+
 OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_CONVT_FWD = 1, 2, 3, 4
 OP_MAXPOOL_FWD, OP_MAXPOOL_BWD, OP_TAIL_FWD, OP_TAIL_BWD = 5, 6, 7, 8
 OP_BN_UPDATE, OP_GRAD_FINAL, OP_BCE, OP_MEMSET = 9, 10, 11, 12
@@ -189,7 +196,8 @@ OP_STEP_TAIL, OP_STEP_INC = 24, 25
 _RECORD_CHECK = [(0, VTensor), (1, Sinks), (2, ConvRec), (3, WgradRec), (4, PoolRec), (5, Tail),
                  (6, TailGrad), (7, BnUpdate), (8, GradFinal), (9, BceRec), (10, Geom), (11, Bn),
                  (12, VSeg), (13, Sink), (14, SumRepRec), (15, KpStem), (16, MaskHead),
-                 (17, StampRec), (18, DwBwdRec), (19, StepTail), (20, TrainSample)]
+                 (17, StampRec), (18, DwBwdRec), (19, StepTail), (20, TrainSample),
+                 (21, TrainAug)]
 
 # exported symbol -> (restype, argtypes)
 SIGNATURES = {
@@ -239,6 +247,9 @@ SIGNATURES = {
     "isg_train_crop": (c_int32, [c_void_p, c_int64, POINTER(TrainSample), c_void_p, c_int32,
                                  c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
+    "isg_train_crop_aug": (c_int32, [c_void_p, c_int64, POINTER(TrainSample), POINTER(TrainAug),
+                                     c_uint64, c_uint64, c_void_p, c_int32, c_int32, c_int32,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "isg_keypoint_heatmaps": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_double,
                                         c_double, c_void_p, c_void_p]),
     "isg_kp_stem_fwd": (c_int32, [POINTER(KpStem), c_void_p]),

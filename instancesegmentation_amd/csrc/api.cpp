@@ -107,7 +107,7 @@ static isg_vtensor resolve_y(const isg_vtensor* v) { return isg_resolve_y(v); } 
 extern "C" {
 
 const char* isg_last_error(void) { return g_last_error.c_str(); }
-int32_t isg_abi_version(void) { return 13; }  // 13: isg_train_crop (train_crop.hip)
+int32_t isg_abi_version(void) { return 14; }  // 14: isg_train_crop_aug (train_crop.hip)
 int32_t isg_stat_replicas(void) { return ISG_STAT_REP; }
 
 int32_t isg_conv_fwd(const isg_conv_geom* g, const isg_vtensor* x_, const float* w,
@@ -694,6 +694,7 @@ int32_t isg_record_size(int32_t which) {
         case 18: return (int32_t)sizeof(DwBwdRec);
         case 19: return (int32_t)sizeof(isg_step_tail_args);
         case 20: return (int32_t)sizeof(isg_train_sample);
+        case 21: return (int32_t)sizeof(isg_train_aug);
         default: return -1;
     }
 }

@@ -26,6 +26,14 @@
 //                      consecutive u per lane, one 16-byte store per plane when V == 4.
 //                      Workgroup 0 of a sample also writes its window and projects its 17
 //                      keypoints through it in double.
+//   train_crop_aug_kernel  stage B of isg_train_crop_aug: the same with one isg_train_aug
+//                      record per sample (augment.py augment_sample is its CPU statement).
+//                      The window's sides are jittered; the output grid is mirrored and/or
+//                      rotated about the crop's centre; contrast, noise and a multiplier act
+//                      on the quantised image planes. blockIdx.y is the sample, so every
+//                      choice (separable or rotated taps, which colour steps, noise at all)
+//                      is uniform in the workgroup. The noise is one Philox4x32-10 call per
+//                      output pixel, its counter the pixel and the sample's ordinal.
 //
 // Sample descriptors are host memory and reach the kernels by value, kChunk to a launch.
 // A tap is loaded only through an index that was made valid first (offset 0 when the tap
@@ -44,6 +52,10 @@ constexpr int kBoxGroups = 2 * kBoxU;       // dwords per thread that size stage
 
 struct TrainChunk {
     isg_train_sample s[kChunk];
+};
+
+struct AugChunk {
+    isg_train_aug a[kChunk];
 };
 
 typedef const uint32_t __attribute__((address_space(1)))* gcu32_p;
@@ -142,23 +154,23 @@ ISG_DEV Tap make_tap(int i, float scale, int lo, int hi, int vlo, int vhi) {
     return t;
 }
 
-ISG_DEV int quantise(float by, float top, float ay, float bot) {
+ISG_DEV int round_u8(float val) {
 #pragma clang fp contract(off)
-    const float val = (by * top) + (ay * bot);
     const int q = (int)(val + 0.5f);
     return q < 0 ? 0 : (q > 255 ? 255 : q);
 }
 
-template <int V>
-__global__ __launch_bounds__(kThreads) void train_crop_kernel(
-    const uint8_t* __restrict__ arena, TrainChunk ch, int base, const int32_t* __restrict__ work,
-    int nbox, const double* __restrict__ kp, int S, float* __restrict__ xo, float* __restrict__ mo,
-    double* __restrict__ kpo, int32_t* __restrict__ wino) {
+ISG_DEV int quantise(float by, float top, float ay, float bot) {
 #pragma clang fp contract(off)
-    __shared__ int s_w[kWaves][8];
-    const int k = blockIdx.y, b = base + k;
-    const int H = ch.s[k].H, W = ch.s[k].W;
-    {   // the max over the nbox slots stage A wrote for this sample (nbox <= 64: two a thread)
+    const float val = (by * top) + (ay * bot);
+    return round_u8(val);
+}
+
+// the pre-pad box of sample b: the max over the nbox slots stage A wrote for it (nbox <= 64:
+// two a thread), then data.py instance_window's three-way choice
+ISG_DEV void sample_box(const int32_t* __restrict__ work, int b, int nbox, int H, int W,
+                        int (*s_w)[8], int& x0, int& y0, int& x1, int& y1) {
+    {
         const int i = threadIdx.x & 7, j = threadIdx.x >> 3;
         const int32_t* slot = work + (int64_t)b * kBoxBlocksMax * 8 + i;
         int r = max(j < nbox ? slot[j * 8] : 0, j + 32 < nbox ? slot[(j + 32) * 8] : 0);
@@ -174,12 +186,25 @@ __global__ __launch_bounds__(kThreads) void train_crop_kernel(
 #pragma unroll
         for (int wv = 0; wv < kWaves; ++wv) w[i] = max(w[i], s_w[wv][i]);
     }
-    int x0 = 0, y0 = 0, x1 = W, y1 = H;  // no mask pixel at all (train_instance.py:163-164)
+    x0 = 0; y0 = 0; x1 = W; y1 = H;  // no mask pixel at all (train_instance.py:163-164)
     if (w[6] > 0) {
         x0 = W - w[4]; y0 = H - w[5]; x1 = w[6]; y1 = w[7];
     } else if (w[2] > 0) {  // every mask pixel was pushed out of the frame
         x0 = W - w[0]; y0 = H - w[1]; x1 = w[2]; y1 = w[3];
     }
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void train_crop_kernel(
+    const uint8_t* __restrict__ arena, TrainChunk ch, int base, const int32_t* __restrict__ work,
+    int nbox, const double* __restrict__ kp, int S, float* __restrict__ xo, float* __restrict__ mo,
+    double* __restrict__ kpo, int32_t* __restrict__ wino) {
+#pragma clang fp contract(off)
+    __shared__ int s_w[kWaves][8];
+    const int k = blockIdx.y, b = base + k;
+    const int H = ch.s[k].H, W = ch.s[k].W;
+    int x0, y0, x1, y1;
+    sample_box(work, b, nbox, H, W, s_w, x0, y0, x1, y1);
     x0 -= ISG_TRAIN_PAD; y0 -= ISG_TRAIN_PAD; x1 += ISG_TRAIN_PAD; y1 += ISG_TRAIN_PAD;
     if (blockIdx.x == 0) {
         if (threadIdx.x < 4)
@@ -237,6 +262,205 @@ __global__ __launch_bounds__(kThreads) void train_crop_kernel(
     }
 }
 
+// ---- stage B with augmentation -------------------------------------------------------
+// a tap pair on the rotated grid: floor and floor + 1, not clamped into the window (it has no
+// meaning there); a tap counts where it lies inside valid
+ISG_DEV Tap free_tap(float f, int vlo, int vhi) {
+#pragma clang fp contract(off)
+    Tap t;
+    const float fl = floorf(f);
+    t.a = f - fl;
+    t.b = 1.f - t.a;
+    t.c0 = (int)fl;  // |f| < 2^31: the window is within 1.2 W + 32 of the image (W < 2^31 / 3)
+    t.c1 = t.c0 + 1;
+    t.o0 = t.c0 >= vlo && t.c0 < vhi;
+    t.o1 = t.c1 >= vlo && t.c1 < vhi;
+    return t;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11), the Random123 constants
+ISG_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                           uint32_t k1, uint32_t out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+ISG_DEV int byte_sum(uint32_t w) {
+    return (int)((w & 255u) + ((w >> 8) & 255u) + ((w >> 16) & 255u) + (w >> 24));
+}
+
+// row of ORDER_PART_NAMES (data.py) that holds the other side's part; the nose is its own
+__constant__ const int kMirrorPart[ISG_TRAIN_PARTS] = {3, 4, 5, 0, 1, 2, 9, 10, 11, 6, 7, 8,
+                                                       13, 12, 14, 16, 15};
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void train_crop_aug_kernel(
+    const uint8_t* __restrict__ arena, TrainChunk ch, AugChunk ag, int base,
+    const int32_t* __restrict__ work, int nbox, const double* __restrict__ kp, int S, uint64_t seed,
+    uint64_t ordinal0, float* __restrict__ xo, float* __restrict__ mo, double* __restrict__ kpo,
+    int32_t* __restrict__ wino) {
+#pragma clang fp contract(off)
+    __shared__ int s_w[kWaves][8];
+    const int k = blockIdx.y, b = base + k;
+    const int H = ch.s[k].H, W = ch.s[k].W;
+    const isg_train_aug& au = ag.a[k];
+    int x0, y0, x1, y1;
+    sample_box(work, b, nbox, H, W, s_w, x0, y0, x1, y1);
+    {   // each side moves by floor(j * a / 1024), |j| <= 1024, a = a fifth of the box: never empty
+        const int64_t ax = (x1 - x0) / 5, ay = (y1 - y0) / 5;
+        x0 += (int)((au.jitter[0] * ax) >> 10) - ISG_TRAIN_PAD;
+        y0 += (int)((au.jitter[1] * ay) >> 10) - ISG_TRAIN_PAD;
+        x1 += (int)((au.jitter[2] * ax) >> 10) + ISG_TRAIN_PAD;
+        y1 += (int)((au.jitter[3] * ay) >> 10) + ISG_TRAIN_PAD;
+    }
+    const bool flip = au.flip != 0;
+    const bool rot = !(au.rot_cos == 1.0 && au.rot_sin == 0.0);
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < 4)
+            wino[4 * b + threadIdx.x] = threadIdx.x == 0 ? x0 : threadIdx.x == 1 ? y0
+                                        : threadIdx.x == 2 ? x1 : y1;
+        if (threadIdx.x < ISG_TRAIN_PARTS) {  // numpy's float64 arithmetic, one op at a time
+            const int part = flip ? kMirrorPart[threadIdx.x] : (int)threadIdx.x;
+            const int64_t i = ((int64_t)b * ISG_TRAIN_PARTS + part) * 3;
+            const int64_t j = ((int64_t)b * ISG_TRAIN_PARTS + threadIdx.x) * 3;
+            double kx = ((kp[i] - (double)x0) * (double)S) / (double)(x1 - x0);
+            double ky = ((kp[i + 1] - (double)y0) * (double)S) / (double)(y1 - y0);
+            if (rot) {  // the inverse of the pixels' map: a keypoint stays on the pixel it marked
+                const double h = (double)S * 0.5, dx = kx - h, dy = ky - h;
+                kx = ((au.rot_cos * dx) + (au.rot_sin * dy)) + h;
+                ky = ((au.rot_cos * dy) - (au.rot_sin * dx)) + h;
+            }
+            if (flip) kx = (double)S - kx;
+            kpo[j] = kx;
+            kpo[j + 1] = ky;
+            kpo[j + 2] = kp[i + 2] > 0.0 ? 1.0 : 0.0;
+        }
+    }
+    const int64_t ss = (int64_t)S * S;
+    const int64_t o = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * V;
+    if (o >= ss) return;
+    const int v = (int)(o / S), u0 = (int)(o - (int64_t)v * S);  // V == 4: S % 4 == 0, one row
+    const int vx0 = max(ch.s[k].valid[0], 0), vy0 = max(ch.s[k].valid[1], 0);
+    const int vx1 = min(ch.s[k].valid[2], W), vy1 = min(ch.s[k].valid[3], H);
+    const uint8_t* img = arena + ch.s[k].img_off;
+    const uint8_t* msk = arena + ch.s[k].mask_off;
+    const float sx = (float)(x1 - x0) / (float)S;
+    const float sy = (float)(y1 - y0) / (float)S;
+    const float rc = (float)au.rot_cos, rs = (float)au.rot_sin, half = (float)S * 0.5f;
+    const float dv = ((float)v + 0.5f) - half;
+    const float alpha = au.contrast, gain = au.noise;
+    const bool noisy = gain != 0.f, per_channel = au.noise_per_channel != 0;
+    const uint64_t ordinal = ordinal0 + (uint64_t)b;
+    Tap ty = make_tap(v, sy, y0, y1, vy0, vy1);  // the separable path's row
+    float r[4][V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const int uu = flip ? S - 1 - (u0 + j) : u0 + j;
+        Tap tx;
+        if (rot) {  // uniform in the workgroup
+            const float du = ((float)uu + 0.5f) - half;
+            const float px = ((rc * du) - (rs * dv)) + half;
+            const float py = ((rs * du) + (rc * dv)) + half;
+            tx = free_tap(((px * sx) - 0.5f) + (float)x0, vx0, vx1);
+            ty = free_tap(((py * sy) - 0.5f) + (float)y0, vy0, vy1);
+        } else {
+            tx = make_tap(uu, sx, x0, x1, vx0, vx1);
+        }
+        const bool k00 = ty.o0 && tx.o0, k01 = ty.o0 && tx.o1;
+        const bool k10 = ty.o1 && tx.o0, k11 = ty.o1 && tx.o1;
+        // pixel index of each tap, 0 (always inside the sample) where the tap is not read
+        const int i00 = k00 ? ty.c0 * W + tx.c0 : 0, i01 = k01 ? ty.c0 * W + tx.c1 : 0;
+        const int i10 = k10 ? ty.c1 * W + tx.c0 : 0, i11 = k11 ? ty.c1 * W + tx.c1 : 0;
+        uint32_t noise[4] = {0u, 0u, 0u, 0u};
+        if (noisy) {
+            const uint64_t pix = (uint64_t)(o + j);
+            philox4x32_10((uint32_t)pix, (uint32_t)(pix >> 32), (uint32_t)ordinal,
+                          (uint32_t)(ordinal >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), noise);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint8_t* p = c < 3 ? img + c : msk;
+            const int st = c < 3 ? 3 : 1;
+            const uint8_t q00 = p[i00 * st], q01 = p[i01 * st], q10 = p[i10 * st], q11 = p[i11 * st];
+            const float s00 = k00 ? (float)q00 : 0.f, s01 = k01 ? (float)q01 : 0.f;
+            const float s10 = k10 ? (float)q10 : 0.f, s11 = k11 ? (float)q11 : 0.f;
+            const float top = (tx.b * s00) + (tx.a * s01);
+            const float bot = (tx.b * s10) + (tx.a * s11);
+            int q = quantise(ty.b, top, ty.a, bot);
+            if (c < 3) {  // each step is the identity on an integer q when its parameter is neutral
+                if (alpha != 1.f) q = round_u8(((float)(q - 127) * alpha) + 127.f);
+                if (noisy) {
+                    const int s = byte_sum(noise[per_channel ? c : 0]);
+                    q = round_u8((float)q + ((float)(s - 510) * gain));
+                }
+                if (au.mult[c] != 1.f) q = round_u8((float)q * au.mult[c]);
+            }
+            r[c][j] = c < 3 ? ((float)q / 255.f - 0.5f) / 0.5f : (float)q / 255.f;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float* dst = c < 3 ? xo + ((int64_t)b * 3 + c) * ss : mo + (int64_t)b * ss;
+        if (V == 4) {
+            gst4(dst, o, f32x4{r[c][0], r[c][1], r[c][2], r[c][3]});
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) gst(dst, o + j, r[c][j]);
+        }
+    }
+}
+
+// the checks of both entries, before any HIP call; max_hw: the largest mask of the first n
+int32_t check_train_args(const char* who, const void* arena, int64_t arena_bytes,
+                         const isg_train_sample* samples, const void* keypoints, int32_t n,
+                         int32_t B, int32_t S, const void* work, const void* x, const void* mask,
+                         const void* kp_out, const void* windows, int64_t* max_hw) {
+    if (!arena || !samples || !keypoints || !work || !x || !mask || !kp_out || !windows)
+        return isg_set_error(ISG_ERR_INVALID, "%s: NULL pointer", who);
+    if (S <= 0 || n < 0 || n > B)
+        return isg_set_error(ISG_ERR_INVALID, "%s: bad sizes S=%d n=%d B=%d", who, S, n, B);
+    *max_hw = 0;
+    for (int i = 0; i < n; ++i) {
+        const isg_train_sample& s = samples[i];
+        if (s.H <= 0 || s.W <= 0)
+            return isg_set_error(ISG_ERR_INVALID, "%s: sample %d is %d x %d", who, i, s.H, s.W);
+        const int64_t hw = (int64_t)s.H * s.W;
+        if (3 * hw >= ((int64_t)1 << 31))
+            return isg_set_error(ISG_ERR_INVALID, "%s: sample %d: 3*H*W = %lld needs < 2^31", who,
+                                 i, (long long)(3 * hw));
+        if (s.img_off < 0 || s.mask_off < 0 || s.img_off > arena_bytes - 3 * hw ||
+            s.mask_off > arena_bytes - hw)
+            return isg_set_error(ISG_ERR_INVALID,
+                                 "%s: sample %d (image at %lld, mask at %lld, %d x %d) "
+                                 "reaches outside the arena of %lld bytes", who, i,
+                                 (long long)s.img_off, (long long)s.mask_off, s.H, s.W,
+                                 (long long)arena_bytes);
+        *max_hw = hw > *max_hw ? hw : *max_hw;
+    }
+    return ISG_OK;
+}
+
+bool aug_value_ok(float v) { return v >= 0.f && v <= ISG_TRAIN_AUG_MAX; }  // false for a NaN
+
+// grid of stage B (false: too many workgroups) and the workgroups per sample of stage A
+bool train_grids(int32_t S, const float* x, const float* mask, int64_t max_hw, bool* wide,
+                 int64_t* crop_blocks, int* box_blocks) {
+    const int64_t ss = (int64_t)S * S;
+    *wide = S % 4 == 0 && (((uintptr_t)x | (uintptr_t)mask) & 15) == 0;
+    *crop_blocks = (ss + (int64_t)kThreads * (*wide ? 4 : 1) - 1) / ((int64_t)kThreads * (*wide ? 4 : 1));
+    const int64_t per_block = (int64_t)kThreads * kBoxGroups * 4;  // mask bytes per workgroup
+    const int bb = (int)((max_hw + per_block - 1) / per_block);
+    *box_blocks = bb < 1 ? 1 : (bb > kBoxBlocksMax ? kBoxBlocksMax : bb);
+    return *crop_blocks <= 0x7fffffff;
+}
+
 }  // namespace
 
 extern "C" {
@@ -248,37 +472,16 @@ int64_t isg_train_crop_workspace(int32_t B) {
 int32_t isg_train_crop(const uint8_t* arena, int64_t arena_bytes, const isg_train_sample* samples,
                        const double* keypoints, int32_t n, int32_t B, int32_t S, void* work,
                        float* x, float* mask, double* kp_out, int32_t* windows, isg_stream_t st) {
-    if (!arena || !samples || !keypoints || !work || !x || !mask || !kp_out || !windows)
-        return isg_set_error(ISG_ERR_INVALID, "train_crop: NULL pointer");
-    if (S <= 0 || n < 0 || n > B)
-        return isg_set_error(ISG_ERR_INVALID, "train_crop: bad sizes S=%d n=%d B=%d", S, n, B);
     int64_t max_hw = 0;
-    for (int i = 0; i < n; ++i) {
-        const isg_train_sample& s = samples[i];
-        if (s.H <= 0 || s.W <= 0)
-            return isg_set_error(ISG_ERR_INVALID, "train_crop: sample %d is %d x %d", i, s.H, s.W);
-        const int64_t hw = (int64_t)s.H * s.W;
-        if (3 * hw >= ((int64_t)1 << 31))
-            return isg_set_error(ISG_ERR_INVALID, "train_crop: sample %d: 3*H*W = %lld needs < 2^31",
-                                 i, (long long)(3 * hw));
-        if (s.img_off < 0 || s.mask_off < 0 || s.img_off > arena_bytes - 3 * hw ||
-            s.mask_off > arena_bytes - hw)
-            return isg_set_error(ISG_ERR_INVALID,
-                                 "train_crop: sample %d (image at %lld, mask at %lld, %d x %d) "
-                                 "reaches outside the arena of %lld bytes", i, (long long)s.img_off,
-                                 (long long)s.mask_off, s.H, s.W, (long long)arena_bytes);
-        max_hw = hw > max_hw ? hw : max_hw;
-    }
+    const int32_t rc = check_train_args("train_crop", arena, arena_bytes, samples, keypoints, n, B,
+                                        S, work, x, mask, kp_out, windows, &max_hw);
+    if (rc != ISG_OK) return rc;
     if (n == 0) return ISG_OK;
-    const int64_t ss = (int64_t)S * S;
-    const bool wide = S % 4 == 0 && (((uintptr_t)x | (uintptr_t)mask) & 15) == 0;
-    const int64_t crop_blocks = (ss + (int64_t)kThreads * (wide ? 4 : 1) - 1) /
-                                ((int64_t)kThreads * (wide ? 4 : 1));
-    if (crop_blocks > 0x7fffffff)
+    bool wide;
+    int64_t crop_blocks;
+    int box_blocks;
+    if (!train_grids(S, x, mask, max_hw, &wide, &crop_blocks, &box_blocks))
         return isg_set_error(ISG_ERR_UNSUPPORTED, "train_crop: %lld workgroups", (long long)crop_blocks);
-    const int64_t per_block = (int64_t)kThreads * kBoxGroups * 4;  // mask bytes per workgroup
-    int box_blocks = (int)((max_hw + per_block - 1) / per_block);
-    box_blocks = box_blocks < 1 ? 1 : (box_blocks > kBoxBlocksMax ? kBoxBlocksMax : box_blocks);
     for (int base = 0; base < n; base += kChunk) {
         const int cnt = n - base < kChunk ? n - base : kChunk;
         TrainChunk ch;
@@ -294,6 +497,63 @@ int32_t isg_train_crop(const uint8_t* arena, int64_t arena_bytes, const isg_trai
                                (const int32_t*)work, box_blocks, keypoints, S, x, mask, kp_out, windows);
     }
     return isg_check_launch("train_crop kernels");
+}
+
+int32_t isg_train_crop_aug(const uint8_t* arena, int64_t arena_bytes, const isg_train_sample* samples,
+                           const isg_train_aug* aug, uint64_t seed, uint64_t ordinal0,
+                           const double* keypoints, int32_t n, int32_t B, int32_t S, void* work,
+                           float* x, float* mask, double* kp_out, int32_t* windows, isg_stream_t st) {
+    int64_t max_hw = 0;
+    const int32_t rc = check_train_args("train_crop_aug", arena, arena_bytes, samples, keypoints, n,
+                                        B, S, work, x, mask, kp_out, windows, &max_hw);
+    if (rc != ISG_OK) return rc;
+    if (!aug) return isg_set_error(ISG_ERR_INVALID, "train_crop_aug: NULL pointer");
+    for (int i = 0; i < n; ++i) {
+        const isg_train_aug& a = aug[i];
+        for (int s = 0; s < 4; ++s)
+            if (a.jitter[s] < -1024 || a.jitter[s] > 1024)
+                return isg_set_error(ISG_ERR_INVALID, "train_crop_aug: record %d: jitter[%d] = %d "
+                                     "outside +/-1024", i, s, a.jitter[s]);
+        const double norm = a.rot_cos * a.rot_cos + a.rot_sin * a.rot_sin - 1.0;
+        if (!(norm >= -1e-6 && norm <= 1e-6))  // also a NaN
+            return isg_set_error(ISG_ERR_INVALID, "train_crop_aug: record %d: (cos, sin) = (%g, %g) "
+                                 "is not a rotation", i, a.rot_cos, a.rot_sin);
+        if ((a.flip != 0 && a.flip != 1) || (a.noise_per_channel != 0 && a.noise_per_channel != 1))
+            return isg_set_error(ISG_ERR_INVALID, "train_crop_aug: record %d: flip = %d, "
+                                 "noise_per_channel = %d (0 or 1)", i, a.flip, a.noise_per_channel);
+        if (!aug_value_ok(a.contrast) || !aug_value_ok(a.noise) || !aug_value_ok(a.mult[0]) ||
+            !aug_value_ok(a.mult[1]) || !aug_value_ok(a.mult[2]))
+            return isg_set_error(ISG_ERR_INVALID, "train_crop_aug: record %d: contrast %g, noise %g, "
+                                 "mult (%g, %g, %g) need to be finite, >= 0 and <= %g", i, a.contrast,
+                                 a.noise, a.mult[0], a.mult[1], a.mult[2], (double)ISG_TRAIN_AUG_MAX);
+    }
+    if (n == 0) return ISG_OK;
+    bool wide;
+    int64_t crop_blocks;
+    int box_blocks;
+    if (!train_grids(S, x, mask, max_hw, &wide, &crop_blocks, &box_blocks))
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "train_crop_aug: %lld workgroups", (long long)crop_blocks);
+    for (int base = 0; base < n; base += kChunk) {
+        const int cnt = n - base < kChunk ? n - base : kChunk;
+        TrainChunk ch;
+        AugChunk ag;
+        for (int i = 0; i < kChunk; ++i) {
+            ch.s[i] = samples[base + (i < cnt ? i : 0)];
+            ag.a[i] = aug[base + (i < cnt ? i : 0)];
+        }
+        hipLaunchKernelGGL(train_box_kernel, dim3((unsigned)box_blocks, (unsigned)cnt),
+                           dim3(kThreads), 0, st, arena, ch, base, (int32_t*)work);
+        const dim3 grid((unsigned)crop_blocks, (unsigned)cnt);
+        if (wide)
+            hipLaunchKernelGGL(train_crop_aug_kernel<4>, grid, dim3(kThreads), 0, st, arena, ch, ag,
+                               base, (const int32_t*)work, box_blocks, keypoints, S, seed, ordinal0,
+                               x, mask, kp_out, windows);
+        else
+            hipLaunchKernelGGL(train_crop_aug_kernel<1>, grid, dim3(kThreads), 0, st, arena, ch, ag,
+                               base, (const int32_t*)work, box_blocks, keypoints, S, seed, ordinal0,
+                               x, mask, kp_out, windows);
+    }
+    return isg_check_launch("train_crop_aug kernels");
 }
 
 }  // extern "C"

@@ -19,6 +19,9 @@ Differences from the reference, all deliberate:
     python -m instancesegmentation_amd.train_loop --train-dataset-dir D --val-dataset-dir V \\
         --checkpoint-dir C [--epoch 30 --batch-size 8 --val-iter 120 --show-iter 20 ...]
         [--gpu-crop]    the loader's crop on the GPU: the workers only decode (gpu_batch.py)
+        [--augment] [--flip] [--augment-seed N]    with --gpu-crop: random jitter, rotation,
+                        contrast, noise and multiply (the reference's list, augment.py) and a
+                        horizontal flip in the crop kernel; training batches only
 """
 import argparse
 import os
@@ -109,7 +112,28 @@ def parse_args(argv=None):
     p.add_argument("--max-steps", type=int, default=0, help="stop after this many steps (0: off)")
     p.add_argument("--gpu-crop", action="store_true",
                    help="workers only decode; mask box, crop and keypoints on the GPU (gpu_batch.py)")
-    return p.parse_args(argv)
+    p.add_argument("--augment", action="store_true",
+                   help="with --gpu-crop: the reference's five random augmentations (augment.py)")
+    p.add_argument("--flip", action="store_true",
+                   help="with --gpu-crop: horizontal flip with probability 0.5")
+    p.add_argument("--augment-seed", type=int, default=None,
+                   help="with --gpu-crop: seed of the draws and the noise (default 0; + rank)")
+    args = p.parse_args(argv)
+    if (args.augment or args.flip or args.augment_seed is not None) and not args.gpu_crop:
+        p.error("--augment, --flip and --augment-seed need --gpu-crop: the augmentation lives in "
+                "the GPU crop kernel, the default CPU loader has none")
+    return args
+
+
+def augment_config(args):
+    """The Augment of the flags, or None: --augment the reference's list, --flip p = 0.5 on
+    top of it or alone."""
+    from .augment import Augment
+    if not (getattr(args, "augment", False) or getattr(args, "flip", False)):
+        return None
+    cfg = Augment() if args.augment else Augment.off()
+    cfg.flip_p = 0.5 if args.flip else 0.0
+    return cfg
 
 
 def _batches(loader, device):
@@ -127,14 +151,15 @@ def _gpu_batches(loader, batcher, trainer=None):
     """--gpu-crop: (inputs, mask, raw batch) per batch of a raw loader, cropped by `batcher`.
     With a trainer the results are written straight into its static input buffers (the batch
     is full: drop_last) and inputs is None — `trainer.step(None, None)` then copies nothing;
-    without one they are views of the batcher's own buffers, valid until its next batch."""
+    without one (the validation form) they are views of the batcher's own buffers, valid until
+    its next batch, and never augmented."""
     for raw in loader:
         if trainer is not None:
             _, _, mask, n = batcher.prepare(raw, trainer.inputs[0], trainer.inputs[1], trainer.target)
             assert n == batcher.B
             yield None, mask, raw
-        else:
-            x, kp, mask, _ = batcher.prepare(raw)
+        else:  # validation: never augmented
+            x, kp, mask, _ = batcher.prepare(raw, augment=False)
             yield [x, kp], mask, raw
 
 
@@ -180,7 +205,8 @@ def fit(args, device=None, process_group=None):
     batcher = None
     if gpu_crop:
         from .gpu_batch import GpuBatcher
-        batcher = GpuBatcher(args.batch_size, S, device)
+        batcher = GpuBatcher(args.batch_size, S, device, augment=augment_config(args),
+                             seed=(getattr(args, "augment_seed", None) or 0) + rank)
 
     def batches(loader, into=None):
         if gpu_crop:

@@ -94,6 +94,45 @@ int main() {
         EXPECT(isg_train_crop(px, nb, &s, kp, 1, 1, 2, wk, x, m, kpo, win, nullptr) == ISG_ERR_INVALID);
         EXPECT(std::strstr(isg_last_error(), "2^31") != nullptr);
     }
+    {   // isg_train_crop_aug: the same checks, then every field of the host records
+        uint8_t px[4 * 6 * 5] = {};
+        double kp[ISG_TRAIN_PARTS * 3] = {}, kpo[ISG_TRAIN_PARTS * 3] = {};
+        int32_t wk[8] = {}, win[4] = {};
+        float x[3 * 4] = {}, m[4] = {};
+        isg_train_sample s{};
+        s.img_off = 0; s.mask_off = 90; s.H = 6; s.W = 5; s.valid[2] = 5; s.valid[3] = 6;
+        isg_train_aug id{};
+        id.rot_cos = 1.0; id.contrast = 1.f; id.mult[0] = id.mult[1] = id.mult[2] = 1.f;
+        const int64_t nb = (int64_t)sizeof(px);
+        auto call = [&](const isg_train_aug& a, int32_t n = 1, int32_t B = 1) {
+            return isg_train_crop_aug(px, nb, &s, &a, 7, 0, kp, n, B, 2, wk, x, m, kpo, win, nullptr);
+        };
+        EXPECT(isg_record_size(21) == (int32_t)sizeof(isg_train_aug) && sizeof(isg_train_aug) == 64);
+        EXPECT(call(id, 0) == ISG_OK);  // n == 0
+        EXPECT(call(id, 2) == ISG_ERR_INVALID);  // n > B
+        EXPECT(isg_train_crop_aug(px, nb, &s, nullptr, 7, 0, kp, 1, 1, 2, wk, x, m, kpo, win, nullptr) ==
+               ISG_ERR_INVALID);
+        EXPECT(isg_train_crop_aug(px, nb - 1, &s, &id, 7, 0, kp, 1, 1, 2, wk, x, m, kpo, win, nullptr) ==
+               ISG_ERR_INVALID);
+        EXPECT(std::strstr(isg_last_error(), "outside the arena") != nullptr);
+        isg_train_aug a = id;
+        a.jitter[3] = 1025;
+        EXPECT(call(a) == ISG_ERR_INVALID && std::strstr(isg_last_error(), "jitter[3]") != nullptr);
+        a = id; a.jitter[0] = -1025;
+        EXPECT(call(a) == ISG_ERR_INVALID);
+        a = id; a.rot_cos = 0.9; a.rot_sin = 0.5;
+        EXPECT(call(a) == ISG_ERR_INVALID && std::strstr(isg_last_error(), "rotation") != nullptr);
+        a = id; a.rot_sin = std::strtod("nan", nullptr);
+        EXPECT(call(a) == ISG_ERR_INVALID);
+        a = id; a.contrast = -1.f;
+        EXPECT(call(a) == ISG_ERR_INVALID);
+        a = id; a.noise = std::strtof("inf", nullptr);
+        EXPECT(call(a) == ISG_ERR_INVALID);
+        a = id; a.mult[2] = std::strtof("nan", nullptr);
+        EXPECT(call(a) == ISG_ERR_INVALID && std::strstr(isg_last_error(), "mult") != nullptr);
+        a = id; a.flip = 2;
+        EXPECT(call(a) == ISG_ERR_INVALID);
+    }
 
     // executor: a malformed record size, an unknown kind, then well-formed records whose
     // launches fail without a device (fix-ups and the side-stream batching run first)

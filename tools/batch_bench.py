@@ -18,6 +18,15 @@ temporary common-format dataset from a seed).
         time per launch, and stage B's write rate (4 planes x S^2 x 4 B x B) over the
         6.29 TB/s HBM streaming rate measured on this part (8.0 TB/s spec). Needs no GPU.
 
+    python tools/batch_bench.py --augment [--rounds 20] [--reps 10] [--fit-steps 30]
+        isg_train_crop_aug beside isg_train_crop in one run, rounds alternating: the kernels
+        of the plain call, of the augmented call with identity records and with every
+        augmentation on (jitter, flip, rotation, contrast, per-channel noise, multiply), by
+        device events; then fit --gpu-crop, fit --gpu-crop --augment --flip and fit --gpu-crop
+        again at the same --cpu-num (the two plain legs give the run-to-run spread).
+        With --replay N it repeats each of the three N times in that order, and --summarise
+        then splits train_crop_aug_kernel's launches into the identity and the full half.
+
 Prints one JSON line per mode.
 """
 import argparse
@@ -107,17 +116,49 @@ def kernels_only(gb, batch):
     return run
 
 
+def full_records(n):
+    """Every augmentation on, a different record per sample."""
+    from instancesegmentation_amd import augment as A
+    cfg = A.Augment(flip_p=1.0, rotate_p=1.0, contrast_p=1.0, noise_p=1.0, noise_per_channel_p=1.0,
+                    multiply_p=1.0, multiply_per_channel_p=1.0, noise_scale=(6.0, 12.75))
+    return A.draw_augment(np.random.Generator(np.random.PCG64(0)), n, cfg)
+
+
+def kernels_only_aug(gb, batch, table):
+    """kernels_only for isg_train_crop_aug with the records `table`."""
+    from instancesegmentation_amd import _lib as L
+    from instancesegmentation_amd.gpu_batch import aug_table, sample_table
+    arena, desc, _ = batch
+    gb.prepare(batch)
+    tab, n, nbytes = sample_table(desc), int(desc.shape[0]), int(arena.numel())
+    recs = aug_table(table)
+    lib, st = L.lib(), L.stream_ptr(gb.device)
+
+    def run():
+        L.check(lib.isg_train_crop_aug(gb.arena.data_ptr(), nbytes, tab, recs, 1, 0,
+                                       gb.kp_in.data_ptr(), n, gb.B, gb.S, gb.work.data_ptr(),
+                                       gb.x.data_ptr(), gb.mask.data_ptr(), gb.keypoints.data_ptr(),
+                                       gb.windows.data_ptr(), st))
+    return run
+
+
 def summarise(d):
     files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
     if not files:
         raise SystemExit(f"no *kernel_trace.csv under {d}")
-    per = {"train_box_kernel": [], "train_crop_kernel": []}
+    per = {"train_box_kernel": [], "train_crop_kernel": [], "train_crop_aug_kernel": []}
     with open(files[0]) as fh:
-        for r in csv.DictReader(fh):
+        for r in sorted(csv.DictReader(fh), key=lambda r: int(r["Start_Timestamp"])):
             for k in per:
                 if k in r["Kernel_Name"]:
                     per[k].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     out = {"trace": files[0]}
+    aug = per.pop("train_crop_aug_kernel")
+    if aug:  # --replay N --augment: N launches with identity records, then N with all on
+        half = len(aug) // 2
+        for name, t in (("stage_b_aug_identity_us", aug[:half]), ("stage_b_aug_full_us", aug[half:])):
+            t = t[len(t) // 4:]
+            out[name] = dict(stats(t), launches=len(t))
     for k, name in (("train_box_kernel", "stage_a_us"), ("train_crop_kernel", "stage_b_us")):
         t = per[k][len(per[k]) // 4:]  # the first quarter is warm-up
         if not t:
@@ -132,7 +173,7 @@ def summarise(d):
     print(json.dumps(out), flush=True)
 
 
-def fit_rate(root, cpu_num, steps, gpu_crop, dev):
+def fit_rate(root, cpu_num, steps, gpu_crop, dev, extra=()):
     """samples/s of fit() between step 3 and the last step (the first two absorb the
     workers' start-up), by the host clock after each synchronised Trainer.step: overall, and
     from the median interval between steps (which leaves out the validation at an epoch's
@@ -154,7 +195,7 @@ def fit_rate(root, cpu_num, steps, gpu_crop, dev):
                                   "--checkpoint-dir", ck, "--batch-size", str(B), "--epoch", "1000",
                                   "--val-iter", "1000000", "--show-iter", "1000000", "--cpu-num",
                                   str(cpu_num), "--max-steps", str(steps)]
-                                 + (["--gpu-crop"] if gpu_crop else []))
+                                 + (["--gpu-crop"] if gpu_crop else []) + list(extra))
             torch.manual_seed(0)
             TL.fit(args, device=dev)
     finally:
@@ -165,6 +206,33 @@ def fit_rate(root, cpu_num, steps, gpu_crop, dev):
             "step_interval_ms": stats(gaps * 1e3)}
 
 
+def augment_legs(args, root, gb, runs, ref, dev):
+    """--augment: the three kernel legs by events, rounds alternating, then the three fits."""
+    runs[1]()  # identity records: the loader's answer again
+    torch.cuda.synchronize(dev)
+    assert torch.equal(gb.x.cpu(), ref[0]) and torch.equal(gb.mask.cpu(), ref[1])
+    names = ("kernels_plain_ms", "kernels_aug_identity_ms", "kernels_aug_full_ms")
+    for run in runs:
+        for _ in range(5):
+            run()
+    torch.cuda.synchronize(dev)
+    t = {k: [] for k in names}
+    for _ in range(args.rounds):
+        for k, run in zip(names, runs):
+            t[k].append(event_ms(run, args.reps))
+    out = {"batch": B, "S": S, "source": [SRC_W, SRC_H], "rounds": args.rounds, "reps": args.reps}
+    out.update({k: stats(v) for k, v in t.items()})
+    print(json.dumps(out), flush=True)
+    if args.fit_steps:
+        out = {"cpu_num": args.cpu_num, "fit_steps": args.fit_steps}
+        for name, extra in (("fit_samples_per_s_gpu_crop", ()),
+                            ("fit_samples_per_s_gpu_crop_augment", ("--augment", "--flip")),
+                            ("fit_samples_per_s_gpu_crop_again", ())):
+            out[name] = fit_rate(root, args.cpu_num, args.fit_steps, True, dev, extra)
+            print(json.dumps(out), flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20)
@@ -173,6 +241,7 @@ def main():
     ap.add_argument("--summarise", default="")
     ap.add_argument("--cpu-num", type=int, default=2)
     ap.add_argument("--fit-steps", type=int, default=30, help="0: skip (v)")
+    ap.add_argument("--augment", action="store_true", help="isg_train_crop_aug beside the plain call")
     ap.add_argument("--images", type=int, default=256, help="dataset size: 32 steps an epoch")
     args = ap.parse_args()
     if args.summarise:
@@ -190,9 +259,14 @@ def main():
                    for r in range(4)]
         gb = GpuBatcher(B, S, dev)
         runs = [kernels_only(gb, b) for b in batches[:1]]
+        if args.augment:
+            from instancesegmentation_amd import augment as A
+            runs.append(kernels_only_aug(gb, batches[0], A.identity_records(B)))
+            runs.append(kernels_only_aug(gb, batches[0], full_records(B)))
         if args.replay:
-            for _ in range(args.replay):
-                runs[0]()
+            for run in runs:
+                for _ in range(args.replay):
+                    run()
             torch.cuda.synchronize(dev)
             print(json.dumps({"replayed": args.replay}), flush=True)
             return 0
@@ -201,6 +275,8 @@ def main():
         ref = D.collate_fn([cpu_ds[i] for i in range(B)])
         assert torch.equal(x.cpu(), ref[0]) and torch.equal(mask.cpu(), ref[1])
         assert torch.equal(kp.cpu(), torch.stack([o["keypoints"] for o in ref[2]]))
+        if args.augment:
+            return augment_legs(args, root, gb, runs, ref, dev)
 
         from instancesegmentation_amd.model.segment import Segment
         from instancesegmentation_amd.train import Trainer
