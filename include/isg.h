@@ -429,6 +429,43 @@ int32_t isg_mask_rle(const uint8_t* masks, int32_t K, int32_t H, int32_t W, cons
                      const int32_t* nsel, int32_t max_sel, uint32_t* runs, int64_t runs_cap,
                      int64_t* offsets /* [max_sel+1] */, void* work, isg_stream_t stream);
 
+/* ---- scoring (csrc/mask_eval.hip) ------------------------ */
+
+/* Crop-space validation IoU counts (the contract is stated on the CPU by
+ * instancesegmentation_amd/evaluate.py `crop_iou_counts_cpu`; it is
+ * train_loop.tensors_mean_iou's tensor2mask followed by >= 128). pred, target: [B][hw]
+ * fp32, any 4-B aligned address. Per sample b, counts[b] = (|P and T|, |P or T|) with
+ *   T = fp32(target * 255) >= 128,   P = fp32(p * 255) >= 128,
+ *   p = pred, or with from_logits != 0 the sigmoid of isg_sigmoid_fwd, 1/(1 + expf(-pred))
+ * (the same device function, so counting the logits equals counting their stored
+ * probabilities bit for bit). One fp32 multiply, no contraction; NaN is background. The
+ * counts are exact integers and are OVERWRITTEN, not accumulated: a caller that validates
+ * several batches passes counts + 2 * offset and reads one table back at the end.
+ * Refused with ISG_ERR_INVALID before any HIP call: B < 0, hw <= 0, and with B > 0 a NULL
+ * pointer, pred / target not 4-B aligned or counts not 8-B aligned. B == 0 does nothing.
+ * Capturable: nothing is allocated or synchronised. */
+int32_t isg_mask_iou_crops(const float* pred, const float* target, int32_t B, int64_t hw,
+                           int32_t from_logits, int64_t* counts /* [B][2] */,
+                           isg_stream_t stream);
+
+/* Detections x ground truth on image canvases (evaluate.py `iou_matrix_cpu`): det [K,H,W]
+ * and gt [G,H,W] uint8 at any byte address, foreground >= 128 (the NMS contract's
+ * threshold). inter[i][j] = |det_i and gt_j|, area_det[i] = |det_i|, area_gt[j] = |gt_j|,
+ * exact integers (H*W < 2^31, else ISG_ERR_INVALID). Both stacks are bit-packed as the
+ * NMS packs its masks (csrc/mask_bits.h), the areas taken in the same pass, then one
+ * workgroup per pair runs AND-popcount over the words.
+ * K == 0 or G == 0 is valid: only the non-empty outputs are written (inter needs both).
+ * K + G <= 65535, more is ISG_ERR_UNSUPPORTED. The result does not depend on what work,
+ * inter or the areas held. Refused before any HIP call: K < 0, G < 0, H <= 0, W <= 0, a
+ * NULL pointer that would be used, work not 8-B aligned.
+ * work: isg_mask_iou_matrix_workspace(K,G,H,W) bytes (-1 for sizes the call refuses),
+ * caller-owned. */
+int64_t isg_mask_iou_matrix_workspace(int32_t K, int32_t G, int32_t H, int32_t W);
+int32_t isg_mask_iou_matrix(const uint8_t* det, int32_t K, const uint8_t* gt, int32_t G,
+                            int32_t H, int32_t W, void* work, int32_t* inter /* [K][G] */,
+                            int32_t* area_det /* [K] */, int32_t* area_gt /* [G] */,
+                            isg_stream_t stream);
+
 /* ---- infer pre-process ----------------------------- */
 
 /* Per-instance crop: window k = (x0,y0,x1,y1) of an HxWx3 uint8 RGB image (instance box

@@ -233,6 +233,10 @@ ISG_DEV float vt_load(const isg_vtensor& vt, const ChanCoef* coef, int n, int c,
     return k.c0 * x + k.c1 * (yv - k.c2) + k.c3;
 }
 
+// The sigmoid of isg_sigmoid_fwd, also what isg_mask_iou_crops thresholds in logit mode:
+// one definition, so a mask counted from logits is the mask of the stored probabilities.
+ISG_DEV float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
+
 // ---- reductions ----------------------------------------------------------------
 ISG_DEV float wave_sum(float v) {
 #pragma unroll

@@ -762,7 +762,7 @@ __global__ __launch_bounds__(kThreads) void bce_kernel(const float* logits, cons
 __global__ void sigmoid_fwd_kernel(const float* x, float* y, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x)
-        y[i] = 1.f / (1.f + expf(-x[i]));
+        y[i] = sigmoid_f(x[i]);
 }
 
 __global__ void sigmoid_bwd_kernel(const float* y, const float* dy, float* dx, int64_t n) {

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mask_bits.h"
 
 namespace {
 
@@ -81,9 +82,8 @@ NmsWork carve(void* work, int K, int64_t words) {
 }
 
 // Bit-packing of mask >= 128, coalesced: a wave reads 256 consecutive bytes (4 per lane)
-// and ballots them into 4 words; word 4g+j holds byte j of every lane of 256-pixel
-// group g. The bit order is internal to the workspace (every mask uses the same one, so
-// AND-popcount intersections are unchanged); counts and sums are exact integers.
+// and ballots them into 4 words (mask_bits.h, shared with mask_eval.hip); counts and sums
+// are exact integers.
 __global__ __launch_bounds__(kThreads) void pack_kernel(const uint8_t* __restrict__ m, int64_t hw,
                                                          int64_t words, NmsWork w) {
     __shared__ unsigned long long sc[4], ss[4];
@@ -94,25 +94,8 @@ __global__ __launch_bounds__(kThreads) void pack_kernel(const uint8_t* __restric
     unsigned long long cnt = 0, sum = 0;
     for (int64_t g = (int64_t)blockIdx.x * 4 + wave; g < groups; g += (int64_t)gridDim.x * 4) {
         const int64_t base = g * 256 + 4 * lane;
-        uint32_t v4 = 0;
-        if (base + 3 < hw && ((hw & 3) == 0)) {
-            v4 = *reinterpret_cast<const uint32_t*>(src + base);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (base + j < hw) v4 |= (uint32_t)src[base + j] << (8 * j);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned v = (v4 >> (8 * j)) & 0xffu;
-            const bool on = v >= 128u;
-            const unsigned long long b = __ballot(on);
-            if (lane == 0) w.bits[(int64_t)k * words + 4 * g + j] = b;
-            if (on) {
-                cnt += 1;
-                sum += v;
-            }
-        }
+        const uint32_t v4 = mask_load_px4(src, base, hw, (hw & 3) == 0);
+        mask_ballot_px4(v4, lane, w.bits + (int64_t)k * words + 4 * g, cnt, sum);
     }
     for (int o = 32; o > 0; o >>= 1) {
         cnt += __shfl_xor(cnt, o, 64);
@@ -176,17 +159,7 @@ __global__ __launch_bounds__(kThreads) void paste_pack_kernel(const float* __res
             for (int j = 0; j < 4; ++j)
                 if (base + j < hw) o[base + j] = (uint8_t)(v4 >> (8 * j));
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned v = (v4 >> (8 * j)) & 0xffu;
-            const bool on = v >= 128u;
-            const unsigned long long b = __ballot(on);
-            if (lane == 0) w.bits[(int64_t)k * words + 4 * g + j] = b;
-            if (on) {
-                cnt += 1;
-                sum += v;
-            }
-        }
+        mask_ballot_px4(v4, lane, w.bits + (int64_t)k * words + 4 * g, cnt, sum);
     }
     for (int off = 32; off > 0; off >>= 1) {
         cnt += __shfl_xor(cnt, off, 64);
@@ -284,8 +257,7 @@ int32_t isg_mask_paste(const float* prob, int32_t K, int32_t S, const int32_t* b
     return isg_check_launch("paste_kernel");
 }
 
-// packed words per mask: 4 per 256-pixel group (pack_kernel)
-static int64_t nms_words(int64_t hw) { return (hw + 255) / 256 * 4; }
+static int64_t nms_words(int64_t hw) { return mask_bit_words(hw); }
 
 int64_t isg_mask_nms_workspace(int32_t K, int32_t H, int32_t W) {
     const int64_t words = nms_words((int64_t)H * W);

@@ -136,6 +136,25 @@ def read_instances(json_path):
             np.asarray(kps, np.float64).reshape(-1, N_PARTS, 3))
 
 
+def read_instance_masks(json_path):
+    """The `instance_mask` path (relative to the dataset root, or None) of every object
+    read_instances returns for the same file, in the same order; a missing file means no
+    instances. The ground truth of `infer --evaluate`."""
+    import json
+    import os
+    if not os.path.exists(json_path):
+        return []
+    with open(json_path) as f:
+        ann = json.load(f)
+    paths = []
+    for obj in ckey(ann, "object", []) or []:
+        cls = ckey(obj, "class")
+        if ckey(obj, "box") is None or (cls is not None and cls != "person"):
+            continue
+        paths.append(ckey(obj, "instance_mask"))
+    return paths
+
+
 def keep_instance(obj):
     """The reference's per-object filter (train_instance.py:102-115): an instance mask,
     body keypoints with more than 9 non-missing parts, class person (if given), a box

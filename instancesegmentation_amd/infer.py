@@ -28,6 +28,7 @@ dropped from `keep`.
 
     python -m instancesegmentation_amd.infer -i IMAGES -o OUT [--continue-test]
         [--checkpoint best.pth] [--max-instances 16] [--format {png,coco}]
+        [--evaluate [--mask-root DIR]]
 
 Instances come from a sidecar annotation next to each image (`<name>.json`, the common
 dataset format of dataset/transfer_coco.py:125-227: {"object": [{"box": [x0,y0,x1,y1],
@@ -38,6 +39,14 @@ kept instance and `<out>/<name>.json` with the kept indices and scores. With
 ("segmentation") and one box ("bbox", [x, y, w, h]) per kept index, and
 `<out>/results.json` is the COCO results list assembled from every per-image JSON in
 the output directory (so `--continue-test` completes it).
+
+`--evaluate` scores the kept masks against the ground truth next to the images: each
+sidecar object's `instance_mask` PNG (a path relative to `--mask-root`, default the image
+directory; objects without one are not ground truth). The kept canvases are matched on the
+GPU while they are still there (evaluate.MaskMatcher, csrc/mask_eval.hip) and accumulated
+into evaluate.MaskAP; `<out>/eval.json` carries the summary (AP, AP50, AP75, AR, ...), per
+image {image, keep, matched_gt@0.5, iou@0.5}, and how many images `--continue-test`
+skipped (only the images processed in this run are scored). Works with either --format.
 """
 import argparse
 import ctypes
@@ -288,6 +297,12 @@ def parse_args(argv=None):
     parser.add_argument("--format", choices=("png", "coco"), default="png",
                         help="png: one PNG per kept instance; coco: COCO RLE results "
                              "(per-image JSON + results.json), no PNGs")
+    parser.add_argument("--evaluate", action="store_true",
+                        help="score the kept masks against the sidecar objects' instance_mask "
+                             "PNGs (mask AP, evaluate.py); writes OUT/eval.json")
+    parser.add_argument("--mask-root", default=None,
+                        help="with --evaluate: directory the instance_mask paths are relative "
+                             "to (default: the image directory)")
     return parser.parse_args(argv)
 
 
@@ -316,11 +331,34 @@ def load_model(checkpoint):
     return m
 
 
+def load_ground_truth(json_path, mask_root, H, W):
+    """(gt uint8 [g,H,W], object indices [g]) of one image for --evaluate: the instance_mask
+    PNG of every sidecar object that has one, in read_instances order."""
+    from PIL import Image
+
+    from .data import read_instance_masks
+    masks, index = [], []
+    for i, rel in enumerate(read_instance_masks(json_path)):
+        if not rel:
+            continue
+        m = np.asarray(Image.open(os.path.join(mask_root, rel)).convert("L"))
+        if m.shape != (H, W):
+            raise ValueError(f"{rel}: instance mask is {m.shape}, the image {(H, W)}")
+        masks.append(m)
+        index.append(i)
+    gt = np.stack(masks) if masks else np.zeros((0, H, W), np.uint8)
+    return np.ascontiguousarray(gt, np.uint8), index
+
+
 def main(argv=None):
     from PIL import Image
 
     from .data import read_instances
     args = parse_args(argv)
+    if args.evaluate:
+        from .evaluate import MaskAP, MaskMatcher
+        ap, matchers, eval_images, skipped = MaskAP(), {}, [], 0
+        mask_root = args.mask_root or args.test_image_dir
     os.makedirs(args.output_dir, exist_ok=True)
     model = load_model(args.checkpoint)
     coco = args.format == "coco"
@@ -329,6 +367,8 @@ def main(argv=None):
         dirname, basename, ext = path_decompose(filepath)
         out_json = os.path.join(args.output_dir, basename + ".json")
         if args.continue_test and os.path.exists(out_json):
+            if args.evaluate:
+                skipped += 1
             continue
         img = np.asarray(Image.open(filepath).convert("RGB"))
         boxes, kps = read_instances(os.path.join(dirname, basename + ".json"))
@@ -354,6 +394,21 @@ def main(argv=None):
             print(f"warning: {basename}: {len(boxes)} instances > {eng.K}: mask-NMS runs per "
                   f"chunk of {eng.K}")
             res["nms"] = f"per chunk of {eng.K}"
+        if args.evaluate:
+            gt, gt_index = load_ground_truth(os.path.join(dirname, basename + ".json"),
+                                             mask_root, H, W)
+            matcher = matchers.get((H, W))
+            if matcher is None or matcher.max_det < eng.K or matcher.max_gt < len(gt):
+                matcher = matchers[(H, W)] = MaskMatcher((H, W), eng.K, max(len(gt), 1),
+                                                         eng.device)
+            gt_dev = torch.from_numpy(gt).to(eng.device)
+            rows, det_scores = [], []
+
+        def match(keep, scores):
+            # the chunk's kept canvases, still on the device, against the image's ground truth
+            det = eng.masks[:eng.n][torch.as_tensor(keep, dtype=torch.long, device=eng.device)]
+            rows.append(matcher.iou(det, gt_dev)[0])
+            det_scores.extend(float(scores[i]) for i in keep)
         if len(boxes):
             for b0 in range(0, len(boxes), eng.K):
                 if coco:
@@ -364,6 +419,8 @@ def main(argv=None):
                     res["scores"] += [float(s) for s in scores]
                     res["segmentation"] += segs
                     res["bbox"] += [R.to_bbox(R.from_string(sg["counts"]), H, W) for sg in segs]
+                    if args.evaluate:
+                        match(keep, scores)
                     continue
                 masks, keep, scores = eng(img, boxes[b0:b0 + eng.K], kps[b0:b0 + eng.K])
                 odir = os.path.join(args.output_dir, basename)
@@ -373,10 +430,27 @@ def main(argv=None):
                     Image.fromarray(host[i]).save(os.path.join(odir, f"{b0 + i}.png"))
                 res["keep"] += [b0 + i for i in keep]
                 res["scores"] += [float(s) for s in scores]
+                if args.evaluate:
+                    match(keep, scores)
         with open(out_json, "w") as f:
             json.dump(res, f)
+        if args.evaluate:
+            # every chunk's matrix on its own, the rows concatenated before matching
+            iou = np.concatenate(rows) if rows else np.zeros((0, len(gt)))
+            m = ap.add_image(det_scores, iou)
+            eval_images.append({"image": res["image"], "keep": res["keep"],
+                                "matched_gt@0.5": [gt_index[j] if j >= 0 else -1
+                                                   for j in m["matched_gt@0.5"]],
+                                "iou@0.5": m["iou@0.5"]})
     if coco:
         R.write_results(args.output_dir)
+    if args.evaluate:
+        summary = ap.summary()
+        with open(os.path.join(args.output_dir, "eval.json"), "w") as f:
+            json.dump({"summary": summary, "skipped": skipped, "images": eval_images}, f)
+        print("eval: " + " ".join(f"{k} {v:.4f}" if isinstance(v, float) else f"{k} {v}"
+                                  for k, v in summary.items())
+              + (f" (skipped {skipped})" if skipped else ""))
     return 0
 
 

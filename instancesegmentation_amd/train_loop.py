@@ -22,6 +22,10 @@ Differences from the reference, all deliberate:
         [--augment] [--flip] [--augment-seed N]    with --gpu-crop: random jitter, rotation,
                         contrast, noise and multiply (the reference's list, augment.py) and a
                         horizontal flip in the crop kernel; training batches only
+        [--val-batches N]    validation batches behind each val_iou: 1 (default) is the
+                        reference's single shuffled batch, 0 the whole validation set
+        [--gpu-iou]     the train-batch and validation IoU counted on the GPU (evaluate.py,
+                        csrc/mask_eval.hip): the same numbers, one read-back per validation
 """
 import argparse
 import os
@@ -31,6 +35,7 @@ import numpy as np
 import torch
 
 from .data import InstanceCommonDataset, collate_fn, raw_collate_fn
+from .evaluate import crop_iou_counts, mean_iou_from_counts
 
 
 def tensor2mask(tensor):
@@ -118,7 +123,15 @@ def parse_args(argv=None):
                    help="with --gpu-crop: horizontal flip with probability 0.5")
     p.add_argument("--augment-seed", type=int, default=None,
                    help="with --gpu-crop: seed of the draws and the noise (default 0; + rank)")
+    p.add_argument("--val-batches", type=int, default=1,
+                   help="validation batches behind each val_iou (default 1, the reference's "
+                        "single shuffled batch; 0: the whole validation set)")
+    p.add_argument("--gpu-iou", action="store_true",
+                   help="count the train-batch and validation IoU on the GPU (evaluate.py): no "
+                        "per-sample copies, one read-back per validation")
     args = p.parse_args(argv)
+    if args.val_batches < 0:
+        p.error("--val-batches needs a count >= 0 (0: the whole validation set)")
     if (args.augment or args.flip or args.augment_seed is not None) and not args.gpu_crop:
         p.error("--augment, --flip and --augment-seed need --gpu-crop: the augmentation lives in "
                 "the GPU crop kernel, the default CPU loader has none")
@@ -213,6 +226,40 @@ def fit(args, device=None, process_group=None):
             return _gpu_batches(loader, batcher, into)
         return _batches(loader, device)
 
+    gpu_iou = bool(getattr(args, "gpu_iou", False))
+    val_batches = int(getattr(args, "val_batches", 1))
+
+    def score(mask):
+        """(train_batch_iou, val_iou): the IoU of the step just taken and the mean IoU over the
+        samples of the first --val-batches validation batches (1: the reference's single
+        batch, :414-415; 0: all of them). --gpu-iou counts on the device
+        (evaluate.crop_iou_counts): the train batch from the logits, every validation
+        batch into its rows of one table, which is copied to the host once at the end."""
+        if gpu_iou:
+            nb = len(valloader) if val_batches == 0 else min(val_batches, len(valloader))
+            B = trainer.logits.shape[0]
+            table = torch.empty((B + nb * args.batch_size, 2), dtype=torch.int64, device=device)
+            crop_iou_counts(trainer.logits, mask, from_logits=True, out=table[:B])
+            off = B
+        else:
+            train_iou = tensors_mean_iou(trainer.probabilities(), mask)
+            ious = []
+        for k, (vxs, vmask, _) in enumerate(batches(valloader)):
+            prob = trainer.predict(vxs)
+            if gpu_iou:
+                n = prob.shape[0]
+                crop_iou_counts(prob.contiguous(), vmask.contiguous(), out=table[off:off + n])
+                off += n
+            else:
+                ious += [mask_iou(tensor2mask(o), tensor2mask(m)) for o, m in zip(prob, vmask)]
+            if val_batches and k + 1 >= val_batches:
+                break
+        if gpu_iou:
+            counts = table[:off].cpu().numpy()  # the one copy of this validation
+            return (mean_iou_from_counts(counts[:B]),
+                    mean_iou_from_counts(counts[B:]) if off > B else 0.0)
+        return train_iou, (mean(ious) if ious else 0.0)
+
     steps = 0
     epoch = start_epoch
     history = []
@@ -233,12 +280,7 @@ def fit(args, device=None, process_group=None):
             if i0 % args.val_iter == 0:
                 train_iou = val_iou = 0.0
                 if rank == 0:
-                    train_iou = tensors_mean_iou(trainer.probabilities(), mask)
-                    val_ious = []
-                    for vxs, vmask, _ in batches(valloader):
-                        val_ious.append(tensors_mean_iou(trainer.predict(vxs), vmask))
-                        break  # the reference validates on one batch (:414-415)
-                    val_iou = mean(val_ious) if val_ious else 0.0
+                    train_iou, val_iou = score(mask)
                     print(f"{branch_name} {device} [epoch {epoch}] [val_num:{len(valset)}]"
                           f" [train_batch_iou: {round(train_iou, 6)}] [val_iou: {round(val_iou, 6)}]")
                 if world > 1:  # every replica takes the same checkpoint decisions
