@@ -20,11 +20,11 @@ import math
 
 import numpy as np
 
-from .data import N_PARTS, ORDER_PART_NAMES, crop_resample, mask_box
+from .data import (N_PARTS, ORDER_PART_NAMES, TRAIN_PAD, blend_taps, crop_resample, instance_box,
+                   round_u8)
 
 JITTER_ONE = 1024                 # a jitter integer j moves a side by floor(j * a / 1024)
 JITTER_DIV = 5                    # a = box extent // 5
-PAD = 16                          # isg.h ISG_TRAIN_PAD
 NOISE_SIGMA = math.sqrt(4 * (256 ** 2 - 1) / 12)  # of the sum of four uniform bytes: 147.80
 VALUE_MAX = 65536.0               # isg.h ISG_TRAIN_AUG_MAX
 
@@ -160,26 +160,13 @@ def noise_sums(S, seed, ordinal):
     return (s - 510).reshape(4, S, S)
 
 
-def _round_u8(val):
-    """The kernels' `quantise` rule: (int)(val + 0.5f), clamped to 0..255."""
-    return np.clip((val + np.float32(0.5)).astype(np.int64), 0, 255)
-
-
 def augment_window(mask, valid, jitter):
     """instance_window's box with the three-way fallback, each side jittered, then +/- 16."""
-    mask = np.asarray(mask)
-    ih, iw = mask.shape[:2]
-    ib = mask_box(mask) or (0, 0, iw, ih)
-    vx0, vy0 = max(int(valid[0]), 0), max(int(valid[1]), 0)
-    vx1, vy1 = min(int(valid[2]), iw), min(int(valid[3]), ih)
-    m = np.zeros_like(mask)
-    if vx1 > vx0 and vy1 > vy0:
-        m[vy0:vy1, vx0:vx1] = mask[vy0:vy1, vx0:vx1]
-    bx0, by0, bx1, by1 = mask_box(m) or ib
+    bx0, by0, bx1, by1 = instance_box(mask, valid)
     ax, ay = (bx1 - bx0) // JITTER_DIV, (by1 - by0) // JITTER_DIV
     j = [int(v) for v in jitter]
-    return (bx0 - PAD + (j[0] * ax) // JITTER_ONE, by0 - PAD + (j[1] * ay) // JITTER_ONE,
-            bx1 + PAD + (j[2] * ax) // JITTER_ONE, by1 + PAD + (j[3] * ay) // JITTER_ONE)
+    return (bx0 - TRAIN_PAD + (j[0] * ax) // JITTER_ONE, by0 - TRAIN_PAD + (j[1] * ay) // JITTER_ONE,
+            bx1 + TRAIN_PAD + (j[2] * ax) // JITTER_ONE, by1 + TRAIN_PAD + (j[3] * ay) // JITTER_ONE)
 
 
 def rot_resample(img, window, valid, size, cos, sin):
@@ -188,13 +175,7 @@ def rot_resample(img, window, valid, size, cos, sin):
     p maps into the image like an output centre: ((p * scale) - 0.5) + lo. Taps at floor and
     floor + 1, not clamped into the window; a tap outside `valid` or the image counts as 0."""
     f32 = np.float32
-    img = np.asarray(img, np.uint8)
-    if img.ndim == 2:
-        img = img[:, :, None]
-    H, W, _ = img.shape
     x0, y0, x1, y1 = (int(v) for v in window)
-    vx0, vy0 = max(int(valid[0]), 0), max(int(valid[1]), 0)
-    vx1, vy1 = min(int(valid[2]), W), min(int(valid[3]), H)
     c, s, half = f32(cos), f32(sin), f32(size) * f32(0.5)
     d = (np.arange(size).astype(f32) + f32(0.5)) - half
     du, dv = d[None, :], d[:, None]
@@ -203,20 +184,8 @@ def rot_resample(img, window, valid, size, cos, sin):
     fx = ((px * (f32(x1 - x0) / f32(size))) - f32(0.5)) + f32(x0)
     fy = ((py * (f32(y1 - y0) / f32(size))) - f32(0.5)) + f32(y0)
     flx, fly = np.floor(fx), np.floor(fy)
-    ax, ay = fx - flx, fy - fly
     ix, iy = flx.astype(np.int64), fly.astype(np.int64)
-
-    def sample(yy, xx):
-        ok = (yy >= vy0) & (yy < vy1) & (xx >= vx0) & (xx < vx1)
-        v = img[np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)].astype(f32)
-        return np.where(ok[:, :, None], v, f32(0.0))
-
-    bx, by = (f32(1.0) - ax)[:, :, None], (f32(1.0) - ay)[:, :, None]
-    axx, ayy = ax[:, :, None], ay[:, :, None]
-    top = (bx * sample(iy, ix)) + (axx * sample(iy, ix + 1))
-    bot = (bx * sample(iy + 1, ix)) + (axx * sample(iy + 1, ix + 1))
-    val = (by * top) + (ayy * bot)
-    return _round_u8(val).astype(np.uint8)
+    return blend_taps(img, valid, (iy, iy + 1), (ix, ix + 1), fy - fly, fx - flx)
 
 
 def colour(q, params, seed, ordinal):
@@ -226,14 +195,14 @@ def colour(q, params, seed, ordinal):
     f32 = np.float32
     S = q.shape[0]
     q = q.astype(np.int64)
-    q = _round_u8(((q - 127).astype(f32) * f32(params["contrast"])) + f32(127.0))
+    q = round_u8(((q - 127).astype(f32) * f32(params["contrast"])) + f32(127.0))
     k = f32(params["noise"])
     if k != 0:
         s = noise_sums(S, seed, ordinal)
         words = [0, 1, 2] if int(params["noise_per_channel"]) else [0, 0, 0]
         s = np.stack([s[w] for w in words], -1)
-        q = _round_u8(q.astype(f32) + (s.astype(f32) * k))
-    q = _round_u8(q.astype(f32) * np.asarray(params["mult"], f32)[None, None, :])
+        q = round_u8(q.astype(f32) + (s.astype(f32) * k))
+    q = round_u8(q.astype(f32) * np.asarray(params["mult"], f32)[None, None, :])
     return q.astype(np.uint8)
 
 

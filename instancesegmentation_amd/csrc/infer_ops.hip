@@ -10,8 +10,8 @@
 // coordinates clamped into the window (cv2's border on the materialised crop), pixels
 // outside the instance's valid rectangle (the image, minus what the centring translation
 // pushed out of the frame) are the fill value 0, the result rounded to uint8 and normalised like
-// ToTensor + Normalize(0.5, 0.5) (train_instance.py:80-85). Every float op is one IEEE
-// op in the oracle's order (contraction off).
+// ToTensor + Normalize(0.5, 0.5) (train_instance.py:80-85). The arithmetic is crop_core.h's,
+// shared with the training crop (train_crop.hip).
 //
 // Heatmaps (train_instance.py:33-68): 17 maps per instance, exp(-(dx^2+dy^2)/sigma^2)
 // evaluated in DOUBLE precision (numpy's float64 e_table) and stored as float32, only for
@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "crop_core.h"
 
 namespace {
 
@@ -44,31 +45,12 @@ __global__ __launch_bounds__(kThreads) void crop_kernel(const uint8_t* __restric
     }
     const float sx = (float)(x1 - x0) / (float)S;
     const float sy = (float)(y1 - y0) / (float)S;
-    const float fx = (((float)u + 0.5f) * sx - 0.5f) + (float)x0;
-    const float fy = (((float)v + 0.5f) * sy - 0.5f) + (float)y0;
-    const float flx = floorf(fx), fly = floorf(fy);
-    const float ax = fx - flx, ay = fy - fly;
-    const int ix = (int)flx, iy = (int)fly;
-    const int cx0 = min(max(ix, x0), x1 - 1), cx1 = min(max(ix + 1, x0), x1 - 1);
-    const int cy0 = min(max(iy, y0), y1 - 1), cy1 = min(max(iy + 1, y0), y1 - 1);
     const int vx0 = max(valid[4 * k], 0), vy0 = max(valid[4 * k + 1], 0);
     const int vx1 = min(valid[4 * k + 2], W), vy1 = min(valid[4 * k + 3], H);
-    const bool ox0 = cx0 >= vx0 && cx0 < vx1, ox1 = cx1 >= vx0 && cx1 < vx1;
-    const bool oy0 = cy0 >= vy0 && cy0 < vy1, oy1 = cy1 >= vy0 && cy1 < vy1;
-    const float bx = 1.f - ax, by = 1.f - ay;
+    const Taps<int64_t> taps(make_tap(u, sx, x0, x1, vx0, vx1), make_tap(v, sy, y0, y1, vy0, vy1),
+                             W);  // H * W is not bounded here: 64-bit indices
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float s00 = (oy0 && ox0) ? (float)img[((int64_t)cy0 * W + cx0) * 3 + c] : 0.f;
-        const float s01 = (oy0 && ox1) ? (float)img[((int64_t)cy0 * W + cx1) * 3 + c] : 0.f;
-        const float s10 = (oy1 && ox0) ? (float)img[((int64_t)cy1 * W + cx0) * 3 + c] : 0.f;
-        const float s11 = (oy1 && ox1) ? (float)img[((int64_t)cy1 * W + cx1) * 3 + c] : 0.f;
-        const float top = (bx * s00) + (ax * s01);
-        const float bot = (bx * s10) + (ax * s11);
-        const float val = (by * top) + (ay * bot);
-        int q = (int)(val + 0.5f);
-        q = q < 0 ? 0 : (q > 255 ? 255 : q);
-        dst[c * ss] = ((float)q / 255.f - 0.5f) / 0.5f;
-    }
+    for (int c = 0; c < 3; ++c) dst[c * ss] = normalise_u8(crop_sample(taps, img + c, 3));
 }
 
 // one block per (instance, part): the keypoint's window only

@@ -17,29 +17,30 @@
 //                      atomic max per wave and bound to a sample's single 32-byte record
 //                      and spent 82 us there for eight 640 x 480 masks) and nothing to clear,
 //                      since every slot that is read was written by the same call.
-//   train_crop_kernel  stage B. Derives the window from those numbers (data.py
-//                      instance_window: the clipped box, else the whole-mask box, else the
-//                      image, then +/- 16) and resamples it to S x S: crop_kernel's
-//                      arithmetic (infer_ops.hip; every float op one IEEE op in the oracle's
-//                      order, contraction off), the coordinates and weights computed once per
-//                      output pixel for the three image planes and the mask plane. V
-//                      consecutive u per lane, one 16-byte store per plane when V == 4.
-//                      Workgroup 0 of a sample also writes its window and projects its 17
-//                      keypoints through it in double.
-//   train_crop_aug_kernel  stage B of isg_train_crop_aug: the same with one isg_train_aug
-//                      record per sample (augment.py augment_sample is its CPU statement).
-//                      The window's sides are jittered; the output grid is mirrored and/or
-//                      rotated about the crop's centre; contrast, noise and a multiplier act
-//                      on the quantised image planes. blockIdx.y is the sample, so every
-//                      choice (separable or rotated taps, which colour steps, noise at all)
-//                      is uniform in the workgroup. The noise is one Philox4x32-10 call per
-//                      output pixel, its counter the pixel and the sample's ordinal.
+//   train_crop_body    stage B, one body for both entries. Derives the window from those
+//                      numbers (data.py instance_box: the clipped box, else the whole-mask
+//                      box, else the image; then +/- 16) and resamples it to S x S with
+//                      crop_core.h's arithmetic (shared with crop_kernel, infer_ops.hip), the
+//                      coordinates and weights computed once per output pixel for the three
+//                      image planes and the mask plane. V consecutive u per lane, one 16-byte
+//                      store per plane when V == 4. Workgroup 0 of a sample also writes its
+//                      window and projects its 17 keypoints through it in double.
+//                      With AUG one isg_train_aug record per sample applies (augment.py
+//                      augment_sample is its CPU statement): the window's sides are jittered;
+//                      the output grid is mirrored and/or rotated about the crop's centre;
+//                      contrast, noise and a multiplier act on the quantised image planes.
+//                      blockIdx.y is the sample, so every choice (separable or rotated taps,
+//                      which colour steps, noise at all) is uniform in the workgroup. The
+//                      noise is one Philox4x32-10 call per output pixel, its counter the
+//                      pixel and the sample's ordinal. Without AUG every one of those
+//                      operands and branches is compiled out (`if constexpr`), not switched
+//                      at run time: the plain kernel takes no record and pays for none.
+//   train_crop_kernel<V>      isg_train_crop's stage B: the body without AUG.
+//   train_crop_aug_kernel<V>  isg_train_crop_aug's stage B: the body with AUG.
 //
 // Sample descriptors are host memory and reach the kernels by value, kChunk to a launch.
-// A tap is loaded only through an index that was made valid first (offset 0 when the tap
-// lies outside valid), so no address outside the sample's image or mask is ever formed
-// into a load.
 #include "common.h"
+#include "crop_core.h"
 
 namespace {
 
@@ -132,42 +133,8 @@ __global__ __launch_bounds__(kThreads) void train_box_kernel(const uint8_t* __re
 }
 
 // ---- stage B -----------------------------------------------------------------------
-struct Tap {        // one output coordinate along one axis
-    float a, b;     // weights of the far and the near tap (a = frac, b = 1 - a)
-    int c0, c1;     // tap coordinates clamped into the window
-    bool o0, o1;    // tap inside valid (and therefore inside the image)
-};
-
-// crop_kernel's coordinate arithmetic (infer_ops.hip), operation for operation
-ISG_DEV Tap make_tap(int i, float scale, int lo, int hi, int vlo, int vhi) {
-#pragma clang fp contract(off)
-    Tap t;
-    const float f = (((float)i + 0.5f) * scale - 0.5f) + (float)lo;
-    const float fl = floorf(f);
-    t.a = f - fl;
-    t.b = 1.f - t.a;
-    const int ii = (int)fl;
-    t.c0 = min(max(ii, lo), hi - 1);
-    t.c1 = min(max(ii + 1, lo), hi - 1);
-    t.o0 = t.c0 >= vlo && t.c0 < vhi;
-    t.o1 = t.c1 >= vlo && t.c1 < vhi;
-    return t;
-}
-
-ISG_DEV int round_u8(float val) {
-#pragma clang fp contract(off)
-    const int q = (int)(val + 0.5f);
-    return q < 0 ? 0 : (q > 255 ? 255 : q);
-}
-
-ISG_DEV int quantise(float by, float top, float ay, float bot) {
-#pragma clang fp contract(off)
-    const float val = (by * top) + (ay * bot);
-    return round_u8(val);
-}
-
 // the pre-pad box of sample b: the max over the nbox slots stage A wrote for it (nbox <= 64:
-// two a thread), then data.py instance_window's three-way choice
+// two a thread), then data.py instance_box's three-way choice
 ISG_DEV void sample_box(const int32_t* __restrict__ work, int b, int nbox, int H, int W,
                         int (*s_w)[8], int& x0, int& y0, int& x1, int& y1) {
     {
@@ -194,90 +161,6 @@ ISG_DEV void sample_box(const int32_t* __restrict__ work, int b, int nbox, int H
     }
 }
 
-template <int V>
-__global__ __launch_bounds__(kThreads) void train_crop_kernel(
-    const uint8_t* __restrict__ arena, TrainChunk ch, int base, const int32_t* __restrict__ work,
-    int nbox, const double* __restrict__ kp, int S, float* __restrict__ xo, float* __restrict__ mo,
-    double* __restrict__ kpo, int32_t* __restrict__ wino) {
-#pragma clang fp contract(off)
-    __shared__ int s_w[kWaves][8];
-    const int k = blockIdx.y, b = base + k;
-    const int H = ch.s[k].H, W = ch.s[k].W;
-    int x0, y0, x1, y1;
-    sample_box(work, b, nbox, H, W, s_w, x0, y0, x1, y1);
-    x0 -= ISG_TRAIN_PAD; y0 -= ISG_TRAIN_PAD; x1 += ISG_TRAIN_PAD; y1 += ISG_TRAIN_PAD;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < 4)
-            wino[4 * b + threadIdx.x] = threadIdx.x == 0 ? x0 : threadIdx.x == 1 ? y0
-                                        : threadIdx.x == 2 ? x1 : y1;
-        if (threadIdx.x < ISG_TRAIN_PARTS) {  // numpy's float64 arithmetic, one op at a time
-            const int64_t j = ((int64_t)b * ISG_TRAIN_PARTS + threadIdx.x) * 3;
-            kpo[j] = ((kp[j] - (double)x0) * (double)S) / (double)(x1 - x0);
-            kpo[j + 1] = ((kp[j + 1] - (double)y0) * (double)S) / (double)(y1 - y0);
-            kpo[j + 2] = kp[j + 2] > 0.0 ? 1.0 : 0.0;
-        }
-    }
-    const int64_t ss = (int64_t)S * S;
-    const int64_t o = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * V;
-    if (o >= ss) return;
-    const int v = (int)(o / S), u0 = (int)(o - (int64_t)v * S);  // V == 4: S % 4 == 0, one row
-    const int vx0 = max(ch.s[k].valid[0], 0), vy0 = max(ch.s[k].valid[1], 0);
-    const int vx1 = min(ch.s[k].valid[2], W), vy1 = min(ch.s[k].valid[3], H);
-    const uint8_t* img = arena + ch.s[k].img_off;
-    const uint8_t* msk = arena + ch.s[k].mask_off;
-    const float sx = (float)(x1 - x0) / (float)S;
-    const float sy = (float)(y1 - y0) / (float)S;
-    const Tap ty = make_tap(v, sy, y0, y1, vy0, vy1);
-    float r[4][V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-        const Tap tx = make_tap(u0 + j, sx, x0, x1, vx0, vx1);
-        const bool k00 = ty.o0 && tx.o0, k01 = ty.o0 && tx.o1;
-        const bool k10 = ty.o1 && tx.o0, k11 = ty.o1 && tx.o1;
-        // pixel index of each tap, 0 (always inside the sample) where the tap is not read
-        const int i00 = k00 ? ty.c0 * W + tx.c0 : 0, i01 = k01 ? ty.c0 * W + tx.c1 : 0;
-        const int i10 = k10 ? ty.c1 * W + tx.c0 : 0, i11 = k11 ? ty.c1 * W + tx.c1 : 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const uint8_t* p = c < 3 ? img + c : msk;
-            const int st = c < 3 ? 3 : 1;
-            const uint8_t q00 = p[i00 * st], q01 = p[i01 * st], q10 = p[i10 * st], q11 = p[i11 * st];
-            const float s00 = k00 ? (float)q00 : 0.f, s01 = k01 ? (float)q01 : 0.f;
-            const float s10 = k10 ? (float)q10 : 0.f, s11 = k11 ? (float)q11 : 0.f;
-            const float top = (tx.b * s00) + (tx.a * s01);
-            const float bot = (tx.b * s10) + (tx.a * s11);
-            const int q = quantise(ty.b, top, ty.a, bot);
-            r[c][j] = c < 3 ? ((float)q / 255.f - 0.5f) / 0.5f : (float)q / 255.f;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        float* dst = c < 3 ? xo + ((int64_t)b * 3 + c) * ss : mo + (int64_t)b * ss;
-        if (V == 4) {
-            gst4(dst, o, f32x4{r[c][0], r[c][1], r[c][2], r[c][3]});
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) gst(dst, o + j, r[c][j]);
-        }
-    }
-}
-
-// ---- stage B with augmentation -------------------------------------------------------
-// a tap pair on the rotated grid: floor and floor + 1, not clamped into the window (it has no
-// meaning there); a tap counts where it lies inside valid
-ISG_DEV Tap free_tap(float f, int vlo, int vhi) {
-#pragma clang fp contract(off)
-    Tap t;
-    const float fl = floorf(f);
-    t.a = f - fl;
-    t.b = 1.f - t.a;
-    t.c0 = (int)fl;  // |f| < 2^31: the window is within 1.2 W + 32 of the image (W < 2^31 / 3)
-    t.c1 = t.c0 + 1;
-    t.o0 = t.c0 >= vlo && t.c0 < vhi;
-    t.o1 = t.c1 >= vlo && t.c1 < vhi;
-    return t;
-}
-
 // Philox4x32-10 (Salmon et al., SC'11), the Random123 constants
 ISG_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                            uint32_t k1, uint32_t out[4]) {
@@ -300,44 +183,50 @@ ISG_DEV int byte_sum(uint32_t w) {
 __constant__ const int kMirrorPart[ISG_TRAIN_PARTS] = {3, 4, 5, 0, 1, 2, 9, 10, 11, 6, 7, 8,
                                                        13, 12, 14, 16, 15};
 
-template <int V>
-__global__ __launch_bounds__(kThreads) void train_crop_aug_kernel(
-    const uint8_t* __restrict__ arena, TrainChunk ch, AugChunk ag, int base,
-    const int32_t* __restrict__ work, int nbox, const double* __restrict__ kp, int S, uint64_t seed,
-    uint64_t ordinal0, float* __restrict__ xo, float* __restrict__ mo, double* __restrict__ kpo,
-    int32_t* __restrict__ wino) {
+// sample b of the call: its descriptor sm and, with AUG, its record au (without AUG au, seed
+// and ordinal0 are never read)
+template <int V, bool AUG>
+ISG_DEV void train_crop_body(const uint8_t* __restrict__ arena, const isg_train_sample& sm,
+                             const isg_train_aug* au, int b, const int32_t* __restrict__ work,
+                             int nbox, const double* __restrict__ kp, int S, uint64_t seed,
+                             uint64_t ordinal0, float* __restrict__ xo, float* __restrict__ mo,
+                             double* __restrict__ kpo, int32_t* __restrict__ wino) {
 #pragma clang fp contract(off)
     __shared__ int s_w[kWaves][8];
-    const int k = blockIdx.y, b = base + k;
-    const int H = ch.s[k].H, W = ch.s[k].W;
-    const isg_train_aug& au = ag.a[k];
+    const int H = sm.H, W = sm.W;
     int x0, y0, x1, y1;
     sample_box(work, b, nbox, H, W, s_w, x0, y0, x1, y1);
-    {   // each side moves by floor(j * a / 1024), |j| <= 1024, a = a fifth of the box: never empty
+    bool flip = false, rot = false;  // constants without AUG: what they guard is compiled out
+    if constexpr (AUG) {
+        // each side moves by floor(j * a / 1024), |j| <= 1024, a = a fifth of the box: never empty
         const int64_t ax = (x1 - x0) / 5, ay = (y1 - y0) / 5;
-        x0 += (int)((au.jitter[0] * ax) >> 10) - ISG_TRAIN_PAD;
-        y0 += (int)((au.jitter[1] * ay) >> 10) - ISG_TRAIN_PAD;
-        x1 += (int)((au.jitter[2] * ax) >> 10) + ISG_TRAIN_PAD;
-        y1 += (int)((au.jitter[3] * ay) >> 10) + ISG_TRAIN_PAD;
+        x0 += (int)((au->jitter[0] * ax) >> 10);
+        y0 += (int)((au->jitter[1] * ay) >> 10);
+        x1 += (int)((au->jitter[2] * ax) >> 10);
+        y1 += (int)((au->jitter[3] * ay) >> 10);
+        flip = au->flip != 0;
+        rot = !(au->rot_cos == 1.0 && au->rot_sin == 0.0);
     }
-    const bool flip = au.flip != 0;
-    const bool rot = !(au.rot_cos == 1.0 && au.rot_sin == 0.0);
+    x0 -= ISG_TRAIN_PAD; y0 -= ISG_TRAIN_PAD; x1 += ISG_TRAIN_PAD; y1 += ISG_TRAIN_PAD;
     if (blockIdx.x == 0) {
         if (threadIdx.x < 4)
             wino[4 * b + threadIdx.x] = threadIdx.x == 0 ? x0 : threadIdx.x == 1 ? y0
                                         : threadIdx.x == 2 ? x1 : y1;
         if (threadIdx.x < ISG_TRAIN_PARTS) {  // numpy's float64 arithmetic, one op at a time
-            const int part = flip ? kMirrorPart[threadIdx.x] : (int)threadIdx.x;
+            int part = (int)threadIdx.x;
+            if constexpr (AUG) part = flip ? kMirrorPart[threadIdx.x] : part;
             const int64_t i = ((int64_t)b * ISG_TRAIN_PARTS + part) * 3;
             const int64_t j = ((int64_t)b * ISG_TRAIN_PARTS + threadIdx.x) * 3;
             double kx = ((kp[i] - (double)x0) * (double)S) / (double)(x1 - x0);
             double ky = ((kp[i + 1] - (double)y0) * (double)S) / (double)(y1 - y0);
-            if (rot) {  // the inverse of the pixels' map: a keypoint stays on the pixel it marked
-                const double h = (double)S * 0.5, dx = kx - h, dy = ky - h;
-                kx = ((au.rot_cos * dx) + (au.rot_sin * dy)) + h;
-                ky = ((au.rot_cos * dy) - (au.rot_sin * dx)) + h;
+            if constexpr (AUG) {
+                if (rot) {  // the inverse of the pixels' map: a keypoint stays on the pixel it marked
+                    const double h = (double)S * 0.5, dx = kx - h, dy = ky - h;
+                    kx = ((au->rot_cos * dx) + (au->rot_sin * dy)) + h;
+                    ky = ((au->rot_cos * dy) - (au->rot_sin * dx)) + h;
+                }
+                if (flip) kx = (double)S - kx;
             }
-            if (flip) kx = (double)S - kx;
             kpo[j] = kx;
             kpo[j + 1] = ky;
             kpo[j + 2] = kp[i + 2] > 0.0 ? 1.0 : 0.0;
@@ -347,62 +236,52 @@ __global__ __launch_bounds__(kThreads) void train_crop_aug_kernel(
     const int64_t o = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * V;
     if (o >= ss) return;
     const int v = (int)(o / S), u0 = (int)(o - (int64_t)v * S);  // V == 4: S % 4 == 0, one row
-    const int vx0 = max(ch.s[k].valid[0], 0), vy0 = max(ch.s[k].valid[1], 0);
-    const int vx1 = min(ch.s[k].valid[2], W), vy1 = min(ch.s[k].valid[3], H);
-    const uint8_t* img = arena + ch.s[k].img_off;
-    const uint8_t* msk = arena + ch.s[k].mask_off;
+    const int vx0 = max(sm.valid[0], 0), vy0 = max(sm.valid[1], 0);
+    const int vx1 = min(sm.valid[2], W), vy1 = min(sm.valid[3], H);
+    const uint8_t* img = arena + sm.img_off;
+    const uint8_t* msk = arena + sm.mask_off;
     const float sx = (float)(x1 - x0) / (float)S;
     const float sy = (float)(y1 - y0) / (float)S;
-    const float rc = (float)au.rot_cos, rs = (float)au.rot_sin, half = (float)S * 0.5f;
-    const float dv = ((float)v + 0.5f) - half;
-    const float alpha = au.contrast, gain = au.noise;
-    const bool noisy = gain != 0.f, per_channel = au.noise_per_channel != 0;
-    const uint64_t ordinal = ordinal0 + (uint64_t)b;
     Tap ty = make_tap(v, sy, y0, y1, vy0, vy1);  // the separable path's row
     float r[4][V];
 #pragma unroll
     for (int j = 0; j < V; ++j) {
-        const int uu = flip ? S - 1 - (u0 + j) : u0 + j;
+        int uu = u0 + j;
         Tap tx;
-        if (rot) {  // uniform in the workgroup
-            const float du = ((float)uu + 0.5f) - half;
-            const float px = ((rc * du) - (rs * dv)) + half;
-            const float py = ((rs * du) + (rc * dv)) + half;
-            tx = free_tap(((px * sx) - 0.5f) + (float)x0, vx0, vx1);
-            ty = free_tap(((py * sy) - 0.5f) + (float)y0, vy0, vy1);
-        } else {
-            tx = make_tap(uu, sx, x0, x1, vx0, vx1);
-        }
-        const bool k00 = ty.o0 && tx.o0, k01 = ty.o0 && tx.o1;
-        const bool k10 = ty.o1 && tx.o0, k11 = ty.o1 && tx.o1;
-        // pixel index of each tap, 0 (always inside the sample) where the tap is not read
-        const int i00 = k00 ? ty.c0 * W + tx.c0 : 0, i01 = k01 ? ty.c0 * W + tx.c1 : 0;
-        const int i10 = k10 ? ty.c1 * W + tx.c0 : 0, i11 = k11 ? ty.c1 * W + tx.c1 : 0;
         uint32_t noise[4] = {0u, 0u, 0u, 0u};
-        if (noisy) {
-            const uint64_t pix = (uint64_t)(o + j);
-            philox4x32_10((uint32_t)pix, (uint32_t)(pix >> 32), (uint32_t)ordinal,
-                          (uint32_t)(ordinal >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), noise);
+        if constexpr (AUG) {
+            if (flip) uu = S - 1 - uu;
+            if (rot) {  // uniform in the workgroup
+                // |f| < 2^31: the window is within 1.2 W + 32 of the image (W < 2^31 / 3)
+                const float rc = (float)au->rot_cos, rs = (float)au->rot_sin, half = (float)S * 0.5f;
+                const float du = ((float)uu + 0.5f) - half, dv = ((float)v + 0.5f) - half;
+                const float px = ((rc * du) - (rs * dv)) + half;
+                const float py = ((rs * du) + (rc * dv)) + half;
+                tx = free_tap(((px * sx) - 0.5f) + (float)x0, vx0, vx1);
+                ty = free_tap(((py * sy) - 0.5f) + (float)y0, vy0, vy1);
+            }
+            if (au->noise != 0.f) {
+                const uint64_t pix = (uint64_t)(o + j), ordinal = ordinal0 + (uint64_t)b;
+                philox4x32_10((uint32_t)pix, (uint32_t)(pix >> 32), (uint32_t)ordinal,
+                              (uint32_t)(ordinal >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), noise);
+            }
         }
+        if (!rot) tx = make_tap(uu, sx, x0, x1, vx0, vx1);
+        const Taps<int> taps(tx, ty, W);  // 3*H*W < 2^31 (checked by the caller)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const uint8_t* p = c < 3 ? img + c : msk;
-            const int st = c < 3 ? 3 : 1;
-            const uint8_t q00 = p[i00 * st], q01 = p[i01 * st], q10 = p[i10 * st], q11 = p[i11 * st];
-            const float s00 = k00 ? (float)q00 : 0.f, s01 = k01 ? (float)q01 : 0.f;
-            const float s10 = k10 ? (float)q10 : 0.f, s11 = k11 ? (float)q11 : 0.f;
-            const float top = (tx.b * s00) + (tx.a * s01);
-            const float bot = (tx.b * s10) + (tx.a * s11);
-            int q = quantise(ty.b, top, ty.a, bot);
-            if (c < 3) {  // each step is the identity on an integer q when its parameter is neutral
-                if (alpha != 1.f) q = round_u8(((float)(q - 127) * alpha) + 127.f);
-                if (noisy) {
-                    const int s = byte_sum(noise[per_channel ? c : 0]);
-                    q = round_u8((float)q + ((float)(s - 510) * gain));
+            int q = c < 3 ? crop_sample(taps, img + c, 3) : crop_sample(taps, msk, 1);
+            if constexpr (AUG) {
+                if (c < 3) {  // each step is the identity on an integer q when its parameter is neutral
+                    if (au->contrast != 1.f) q = round_u8(((float)(q - 127) * au->contrast) + 127.f);
+                    if (au->noise != 0.f) {
+                        const int s = byte_sum(noise[au->noise_per_channel != 0 ? c : 0]);
+                        q = round_u8((float)q + ((float)(s - 510) * au->noise));
+                    }
+                    if (au->mult[c] != 1.f) q = round_u8((float)q * au->mult[c]);
                 }
-                if (au.mult[c] != 1.f) q = round_u8((float)q * au.mult[c]);
             }
-            r[c][j] = c < 3 ? ((float)q / 255.f - 0.5f) / 0.5f : (float)q / 255.f;
+            r[c][j] = c < 3 ? normalise_u8(q) : (float)q / 255.f;
         }
     }
 #pragma unroll
@@ -417,6 +296,28 @@ __global__ __launch_bounds__(kThreads) void train_crop_aug_kernel(
     }
 }
 
+template <int V>
+__global__ __launch_bounds__(kThreads) void train_crop_kernel(
+    const uint8_t* __restrict__ arena, TrainChunk ch, int base, const int32_t* __restrict__ work,
+    int nbox, const double* __restrict__ kp, int S, float* __restrict__ xo, float* __restrict__ mo,
+    double* __restrict__ kpo, int32_t* __restrict__ wino) {
+    const int k = blockIdx.y;
+    train_crop_body<V, false>(arena, ch.s[k], nullptr, base + k, work, nbox, kp, S, 0, 0, xo, mo, kpo,
+                              wino);
+}
+
+template <int V>
+__global__ __launch_bounds__(kThreads) void train_crop_aug_kernel(
+    const uint8_t* __restrict__ arena, TrainChunk ch, AugChunk ag, int base,
+    const int32_t* __restrict__ work, int nbox, const double* __restrict__ kp, int S, uint64_t seed,
+    uint64_t ordinal0, float* __restrict__ xo, float* __restrict__ mo, double* __restrict__ kpo,
+    int32_t* __restrict__ wino) {
+    const int k = blockIdx.y;
+    train_crop_body<V, true>(arena, ch.s[k], &ag.a[k], base + k, work, nbox, kp, S, seed, ordinal0, xo,
+                             mo, kpo, wino);
+}
+
+// ---- host ----------------------------------------------------------------------------
 // the checks of both entries, before any HIP call; max_hw: the largest mask of the first n
 int32_t check_train_args(const char* who, const void* arena, int64_t arena_bytes,
                          const isg_train_sample* samples, const void* keypoints, int32_t n,
@@ -449,16 +350,45 @@ int32_t check_train_args(const char* who, const void* arena, int64_t arena_bytes
 
 bool aug_value_ok(float v) { return v >= 0.f && v <= ISG_TRAIN_AUG_MAX; }  // false for a NaN
 
-// grid of stage B (false: too many workgroups) and the workgroups per sample of stage A
-bool train_grids(int32_t S, const float* x, const float* mask, int64_t max_hw, bool* wide,
-                 int64_t* crop_blocks, int* box_blocks) {
-    const int64_t ss = (int64_t)S * S;
-    *wide = S % 4 == 0 && (((uintptr_t)x | (uintptr_t)mask) & 15) == 0;
-    *crop_blocks = (ss + (int64_t)kThreads * (*wide ? 4 : 1) - 1) / ((int64_t)kThreads * (*wide ? 4 : 1));
-    const int64_t per_block = (int64_t)kThreads * kBoxGroups * 4;  // mask bytes per workgroup
-    const int bb = (int)((max_hw + per_block - 1) / per_block);
-    *box_blocks = bb < 1 ? 1 : (bb > kBoxBlocksMax ? kBoxBlocksMax : bb);
-    return *crop_blocks <= 0x7fffffff;
+// Both entries after their checks: kChunk samples to a launch of stage A and of stage B, the
+// 16-byte-store stage B where S % 4 == 0 and x and mask are 16-byte aligned. aug NULL: the
+// plain kernels (seed and ordinal0 are then unused).
+int32_t launch_train_crop(const uint8_t* arena, const isg_train_sample* samples,
+                          const isg_train_aug* aug, uint64_t seed, uint64_t ordinal0,
+                          const double* keypoints, int32_t n, int32_t S, int64_t max_hw, void* work,
+                          float* x, float* mask, double* kp_out, int32_t* windows, isg_stream_t st) {
+    if (n == 0) return ISG_OK;
+    const bool wide = S % 4 == 0 && (((uintptr_t)x | (uintptr_t)mask) & 15) == 0;
+    const int64_t per_crop = (int64_t)kThreads * (wide ? 4 : 1);  // outputs per workgroup of stage B
+    const int64_t crop_blocks = ((int64_t)S * S + per_crop - 1) / per_crop;
+    if (crop_blocks > 0x7fffffff)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "%s: %lld workgroups",
+                             aug ? "train_crop_aug" : "train_crop", (long long)crop_blocks);
+    const int64_t per_box = (int64_t)kThreads * kBoxGroups * 4;  // mask bytes per workgroup of stage A
+    const int64_t bb = (max_hw + per_box - 1) / per_box;
+    const int box_blocks = bb < 1 ? 1 : (bb > kBoxBlocksMax ? kBoxBlocksMax : (int)bb);
+    const auto plain_kernel = wide ? train_crop_kernel<4> : train_crop_kernel<1>;
+    const auto aug_kernel = wide ? train_crop_aug_kernel<4> : train_crop_aug_kernel<1>;
+    for (int base = 0; base < n; base += kChunk) {
+        const int cnt = n - base < kChunk ? n - base : kChunk;
+        TrainChunk ch;
+        AugChunk ag;
+        for (int i = 0; i < kChunk; ++i) {
+            ch.s[i] = samples[base + (i < cnt ? i : 0)];
+            if (aug) ag.a[i] = aug[base + (i < cnt ? i : 0)];
+        }
+        hipLaunchKernelGGL(train_box_kernel, dim3((unsigned)box_blocks, (unsigned)cnt),
+                           dim3(kThreads), 0, st, arena, ch, base, (int32_t*)work);
+        const dim3 grid((unsigned)crop_blocks, (unsigned)cnt);
+        if (aug)
+            hipLaunchKernelGGL(aug_kernel, grid, dim3(kThreads), 0, st, arena, ch, ag, base,
+                               (const int32_t*)work, box_blocks, keypoints, S, seed, ordinal0, x, mask,
+                               kp_out, windows);
+        else
+            hipLaunchKernelGGL(plain_kernel, grid, dim3(kThreads), 0, st, arena, ch, base,
+                               (const int32_t*)work, box_blocks, keypoints, S, x, mask, kp_out, windows);
+    }
+    return isg_check_launch(aug ? "train_crop_aug kernels" : "train_crop kernels");
 }
 
 }  // namespace
@@ -476,27 +406,8 @@ int32_t isg_train_crop(const uint8_t* arena, int64_t arena_bytes, const isg_trai
     const int32_t rc = check_train_args("train_crop", arena, arena_bytes, samples, keypoints, n, B,
                                         S, work, x, mask, kp_out, windows, &max_hw);
     if (rc != ISG_OK) return rc;
-    if (n == 0) return ISG_OK;
-    bool wide;
-    int64_t crop_blocks;
-    int box_blocks;
-    if (!train_grids(S, x, mask, max_hw, &wide, &crop_blocks, &box_blocks))
-        return isg_set_error(ISG_ERR_UNSUPPORTED, "train_crop: %lld workgroups", (long long)crop_blocks);
-    for (int base = 0; base < n; base += kChunk) {
-        const int cnt = n - base < kChunk ? n - base : kChunk;
-        TrainChunk ch;
-        for (int i = 0; i < kChunk; ++i) ch.s[i] = samples[base + (i < cnt ? i : 0)];
-        hipLaunchKernelGGL(train_box_kernel, dim3((unsigned)box_blocks, (unsigned)cnt),
-                           dim3(kThreads), 0, st, arena, ch, base, (int32_t*)work);
-        const dim3 grid((unsigned)crop_blocks, (unsigned)cnt);
-        if (wide)
-            hipLaunchKernelGGL(train_crop_kernel<4>, grid, dim3(kThreads), 0, st, arena, ch, base,
-                               (const int32_t*)work, box_blocks, keypoints, S, x, mask, kp_out, windows);
-        else
-            hipLaunchKernelGGL(train_crop_kernel<1>, grid, dim3(kThreads), 0, st, arena, ch, base,
-                               (const int32_t*)work, box_blocks, keypoints, S, x, mask, kp_out, windows);
-    }
-    return isg_check_launch("train_crop kernels");
+    return launch_train_crop(arena, samples, nullptr, 0, 0, keypoints, n, S, max_hw, work, x, mask,
+                             kp_out, windows, st);
 }
 
 int32_t isg_train_crop_aug(const uint8_t* arena, int64_t arena_bytes, const isg_train_sample* samples,
@@ -527,33 +438,8 @@ int32_t isg_train_crop_aug(const uint8_t* arena, int64_t arena_bytes, const isg_
                                  "mult (%g, %g, %g) need to be finite, >= 0 and <= %g", i, a.contrast,
                                  a.noise, a.mult[0], a.mult[1], a.mult[2], (double)ISG_TRAIN_AUG_MAX);
     }
-    if (n == 0) return ISG_OK;
-    bool wide;
-    int64_t crop_blocks;
-    int box_blocks;
-    if (!train_grids(S, x, mask, max_hw, &wide, &crop_blocks, &box_blocks))
-        return isg_set_error(ISG_ERR_UNSUPPORTED, "train_crop_aug: %lld workgroups", (long long)crop_blocks);
-    for (int base = 0; base < n; base += kChunk) {
-        const int cnt = n - base < kChunk ? n - base : kChunk;
-        TrainChunk ch;
-        AugChunk ag;
-        for (int i = 0; i < kChunk; ++i) {
-            ch.s[i] = samples[base + (i < cnt ? i : 0)];
-            ag.a[i] = aug[base + (i < cnt ? i : 0)];
-        }
-        hipLaunchKernelGGL(train_box_kernel, dim3((unsigned)box_blocks, (unsigned)cnt),
-                           dim3(kThreads), 0, st, arena, ch, base, (int32_t*)work);
-        const dim3 grid((unsigned)crop_blocks, (unsigned)cnt);
-        if (wide)
-            hipLaunchKernelGGL(train_crop_aug_kernel<4>, grid, dim3(kThreads), 0, st, arena, ch, ag,
-                               base, (const int32_t*)work, box_blocks, keypoints, S, seed, ordinal0,
-                               x, mask, kp_out, windows);
-        else
-            hipLaunchKernelGGL(train_crop_aug_kernel<1>, grid, dim3(kThreads), 0, st, arena, ch, ag,
-                               base, (const int32_t*)work, box_blocks, keypoints, S, seed, ordinal0,
-                               x, mask, kp_out, windows);
-    }
-    return isg_check_launch("train_crop_aug kernels");
+    return launch_train_crop(arena, samples, aug, seed, ordinal0, keypoints, n, S, max_hw, work, x,
+                             mask, kp_out, windows, st);
 }
 
 }  // extern "C"

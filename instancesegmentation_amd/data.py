@@ -194,62 +194,82 @@ def centring_valid(box, height, width):
     return max(0, -tx), max(0, -ty), min(width, width - tx), min(height, height - ty)
 
 
+def round_u8(val):
+    """The kernels' `round_u8` (csrc/crop_core.h): (int)(val + 0.5f), clamped to 0..255."""
+    return np.clip((val + np.float32(0.5)).astype(np.int64), 0, 255)
+
+
+def blend_taps(img, valid, ys, xs, ay, ax):
+    """The four-tap blend of the crop contract (csrc/crop_core.h crop_sample), shared by
+    crop_resample and augment.rot_resample. img: uint8 [H,W] or [H,W,C]. ys = (rows of the
+    near taps, rows of the far taps) and xs likewise for the columns: integer arrays that
+    broadcast, with the far taps' float32 weights ay and ax, to the output grid. A tap outside
+    `valid` or the image counts as 0. One float32 operation at a time in the oracle's order,
+    rounded half up. Returns uint8 [..., C]."""
+    f32 = np.float32
+    img = np.asarray(img, np.uint8)
+    if img.ndim == 2:
+        img = img[:, :, None]
+    H, W, _ = img.shape
+    vx0, vy0 = max(int(valid[0]), 0), max(int(valid[1]), 0)
+    vx1, vy1 = min(int(valid[2]), W), min(int(valid[3]), H)
+
+    def sample(yy, xx):
+        ok = (yy >= vy0) & (yy < vy1) & (xx >= vx0) & (xx < vx1)
+        v = img[np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)].astype(f32)
+        return np.where(ok[..., None], v, f32(0.0))
+
+    ax, ay = ax[..., None], ay[..., None]
+    bx, by = f32(1.0) - ax, f32(1.0) - ay
+    top = (bx * sample(ys[0], xs[0])) + (ax * sample(ys[0], xs[1]))
+    bot = (bx * sample(ys[1], xs[0])) + (ax * sample(ys[1], xs[1]))
+    return round_u8((by * top) + (ay * bot)).astype(np.uint8)
+
+
 def crop_resample(img, window, valid, size):
     """CPU form of the crop contract (csrc/infer_ops.hip, oracle/infer_oracle.py):
     window [x0,x1)x[y0,y1) of an HxWxC uint8 image, half-pixel-centre bilinear to
     size x size, coordinates clamped into the window, pixels outside `valid` = 0,
     rounded half up to uint8. Returns uint8 [size, size, C]."""
     f32 = np.float32
-    img = np.asarray(img, np.uint8)
-    if img.ndim == 2:
-        img = img[:, :, None]
-    H, W, C = img.shape
     x0, y0, x1, y1 = (int(v) for v in window)
     if x1 <= x0 or y1 <= y0:
-        return np.zeros((size, size, C), np.uint8)
-    vx0, vy0 = max(int(valid[0]), 0), max(int(valid[1]), 0)
-    vx1, vy1 = min(int(valid[2]), W), min(int(valid[3]), H)
+        return np.zeros((size, size) + (np.shape(img)[2:] or (1,)), np.uint8)
     u = np.arange(size).astype(f32)
     fx = ((u + f32(0.5)) * (f32(x1 - x0) / f32(size)) - f32(0.5)) + f32(x0)
     fy = ((u + f32(0.5)) * (f32(y1 - y0) / f32(size)) - f32(0.5)) + f32(y0)
     flx, fly = np.floor(fx), np.floor(fy)
-    ax, ay = fx - flx, fy - fly
     ix, iy = flx.astype(np.int64), fly.astype(np.int64)
-    cx = [np.clip(ix, x0, x1 - 1), np.clip(ix + 1, x0, x1 - 1)]
-    cy = [np.clip(iy, y0, y1 - 1), np.clip(iy + 1, y0, y1 - 1)]
-
-    def sample(yy, xx):
-        ok = ((yy >= vy0) & (yy < vy1))[:, None] & ((xx >= vx0) & (xx < vx1))[None, :]
-        v = img[np.clip(yy, 0, H - 1)[:, None], np.clip(xx, 0, W - 1)[None, :]].astype(f32)
-        return np.where(ok[:, :, None], v, f32(0.0))
-
-    bx, by = (f32(1.0) - ax)[None, :, None], (f32(1.0) - ay)[:, None, None]
-    axx, ayy = ax[None, :, None], ay[:, None, None]
-    top = (bx * sample(cy[0], cx[0])) + (axx * sample(cy[0], cx[1]))
-    bot = (bx * sample(cy[1], cx[0])) + (axx * sample(cy[1], cx[1]))
-    val = (by * top) + (ayy * bot)
-    return np.clip((val + f32(0.5)).astype(np.int64), 0, 255).astype(np.uint8)
+    xs = [np.clip(i, x0, x1 - 1)[None, :] for i in (ix, ix + 1)]  # separable: a row of columns
+    ys = [np.clip(i, y0, y1 - 1)[:, None] for i in (iy, iy + 1)]  # and a column of rows
+    return blend_taps(img, valid, ys, xs, (fy - fly)[:, None], (fx - flx)[None, :])
 
 
-def instance_window(mask, valid, pad=16):
-    """The crop window (x0, y0, x1, y1) of one sample (train_instance.py:148-166): the box of
-    the mask's non-zero pixels that the centring translation leaves in the frame (`valid`,
-    clamped to the image), else, when it pushed all of them out, the box of the whole mask,
-    else the whole image (:163-164); then +/- pad. The CPU statement of stage A of
-    isg_train_crop (csrc/train_crop.hip)."""
+TRAIN_PAD = 16  # train_instance.py:167; isg.h ISG_TRAIN_PAD
+
+
+def instance_box(mask, valid):
+    """The box that instance_window pads and augment.augment_window jitters: its three-way
+    choice, before the pad."""
     mask = np.asarray(mask)
     ih, iw = mask.shape[:2]
-    ib = mask_box(mask)
-    if ib is None:
-        ib = (0, 0, iw, ih)
     vx0, vy0 = max(int(valid[0]), 0), max(int(valid[1]), 0)
     vx1, vy1 = min(int(valid[2]), iw), min(int(valid[3]), ih)
     # a mask pixel pushed out of the frame by the translation is gone before mask2box
     m = np.zeros_like(mask)
     if vx1 > vx0 and vy1 > vy0:
         m[vy0:vy1, vx0:vx1] = mask[vy0:vy1, vx0:vx1]
-    ib = mask_box(m) or ib
-    return ib[0] - pad, ib[1] - pad, ib[2] + pad, ib[3] + pad
+    return mask_box(m) or mask_box(mask) or (0, 0, iw, ih)
+
+
+def instance_window(mask, valid, pad=TRAIN_PAD):
+    """The crop window (x0, y0, x1, y1) of one sample (train_instance.py:148-166): the box of
+    the mask's non-zero pixels that the centring translation leaves in the frame (`valid`,
+    clamped to the image), else, when it pushed all of them out, the box of the whole mask,
+    else the whole image (:163-164); then +/- pad. The CPU statement of stage A of
+    isg_train_crop (csrc/train_crop.hip)."""
+    x0, y0, x1, y1 = instance_box(mask, valid)
+    return x0 - pad, y0 - pad, x1 + pad, y1 + pad
 
 
 class InstanceCommonDataset(torch.utils.data.Dataset):
@@ -309,7 +329,7 @@ class InstanceCommonDataset(torch.utils.data.Dataset):
         if self.raw:
             return (np.ascontiguousarray(image), np.ascontiguousarray(mask),
                     np.asarray(valid, np.int64), kp)
-        win = instance_window(mask, valid, pad=16)
+        win = instance_window(mask, valid)
         S = self.out_size[0]
         img_c = crop_resample(image, win, valid, S)
         mask_c = crop_resample(mask, win, valid, S)[:, :, 0]

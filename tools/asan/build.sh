@@ -19,7 +19,8 @@ for s in "$ROOT"/instancesegmentation_amd/csrc/*.hip "$ROOT"/instancesegmentatio
   o="$OUT/$(basename "${s%.*}").o"
   objs+=("$o")
   if [ -f "$o" ] && [ "$o" -nt "$s" ] && [ "$o" -nt "$ROOT/instancesegmentation_amd/csrc/common.h" ] \
-     && [ "$o" -nt "$ROOT/instancesegmentation_amd/csrc/stage.h" ] && [ "$o" -nt "$ROOT/include/isg.h" ]; then
+     && [ "$o" -nt "$ROOT/instancesegmentation_amd/csrc/stage.h" ] \
+     && [ "$o" -nt "$ROOT/instancesegmentation_amd/csrc/crop_core.h" ] && [ "$o" -nt "$ROOT/include/isg.h" ]; then
     continue
   fi
   lang=""; case "$s" in *.cpp) lang="-x hip";; esac
