@@ -258,13 +258,35 @@ int32_t isg_sum_replicas(float* dst, const double* src, int64_t n, int32_t nrep,
 int32_t isg_convT_fwd(const isg_conv_geom* g, const isg_vtensor* x, const float* w,
                       const isg_sinks* out, isg_stream_t stream);
 
-/* Max-pool k x k stride k (segment.py:29, 145) of a virtual tensor into a slice. */
+/* Max-pool k x k stride k (segment.py:29, 145) of a virtual tensor into a slice: channels
+ * [0, C) of `out` at out_n_stride per image. torch CPU max_pool2d semantics: the first
+ * maximum of a window wins, a NaN wins over everything before it.
+ * ISG_ERR_UNSUPPORTED before any launch: H or W not a multiple of k, a residual input
+ * form, nseg outside 1..ISG_MAX_SEGS, a segment without channels, more than ISG_MAX_CH
+ * channels in all. With k = 2 / 4 each window row is read as one 8-B / 16-B load when
+ * every segment's p is aligned to that and its n_stride a multiple of k; otherwise pixel
+ * by pixel, in the same order with the same result. */
 int32_t isg_maxpool_fwd(const isg_vtensor* x, int32_t k, float* out, int64_t out_n_stride,
                         isg_stream_t stream);
-/* Route dL/d out to the arg-max of each window (first max wins, torch CPU semantics). */
+/* Route dL/d out to the arg-max of each window (same rule). A STORE sink receives zeros
+ * off the arg-max, an ACCUM sink is touched at the arg-max only, a NONE sink not at all.
+ * Refused as the forward, and with ISG_ERR_UNSUPPORTED too: an ACTBWD sink, nsink outside
+ * 1..ISG_MAX_SEGS, sinks that do not cover [0, C) in order (s[0].c0 = 0,
+ * s[i].c0 = s[i-1].c0 + s[i-1].C, the last ending at C). Sinks need not split where the
+ * segments do. */
 int32_t isg_maxpool_bwd(const isg_vtensor* x, int32_t k, const float* dout,
                         int64_t dout_n_stride, const isg_sinks* dx, isg_stream_t stream);
 
+/* Residual tail (isg_tail above) and its backward: g = dL/d(sum) = dout * act'(sum) into
+ * `g`, into every PLAIN term's dterm (an x2-upsampled term receives its 2x2 block's sum)
+ * and, for every BN_FWD term with statistics, gsum / gxsum (centred on that term's own
+ * mean) into its bn.stats; the PReLU slope gradient into slope_grad. g, a PLAIN term's
+ * dterm and slope_grad may each be NULL: nothing is written for it.
+ * ISG_ERR_UNSUPPORTED before any launch: odd H or W, nterm outside 1..3, a residual term
+ * form, a BN_BWD term (the kernels load no saved output y), and in the backward a BN_FWD
+ * term whose own act is not ISG_ACT_NONE (the forward applies it; the backward passes g
+ * to the term unchanged, which is the gradient only without it). ISG_ERR_INVALID: two
+ * terms sharing a gradient destination of which one accumulates. */
 int32_t isg_tail_fwd(const isg_tail* t, isg_stream_t stream);
 int32_t isg_tail_bwd(const isg_tail_grad* t, isg_stream_t stream);
 

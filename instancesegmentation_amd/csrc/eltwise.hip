@@ -466,6 +466,7 @@ struct PoolArgs {
     const float* dout;
     int64_t dout_n_stride;
     isg_sinks dx;
+    int vec;  // forward, k = 2 / 4: every segment's rows take the 8-B / 16-B loads (pool_vec_ok)
 };
 
 template <bool BWD>
@@ -492,7 +493,7 @@ __global__ __launch_bounds__(kThreads) void maxpool_kernel(PoolArgs a) {
         const int cb = s == 0 ? 0 : (s == 1 ? a.x.s[0].C : a.x.s[0].C + a.x.s[1].C);
         const isg_vseg& sg = s == 0 ? a.x.s[0] : (s == 1 ? a.x.s[1] : a.x.s[2]);
         const int xf = sg.xform, act = sg.act;
-        if ((k == 4 || k == 2) && xf != ISG_XF_BN_BWD) {
+        if (a.vec && xf != ISG_XF_BN_BWD) {
             const float* base = sg.p + (int64_t)n * sg.n_stride + (int64_t)(c - cb) * hw;
             const ChanCoef kc = coef[c];
             auto tf = [&](float x) {
@@ -549,6 +550,27 @@ __global__ __launch_bounds__(kThreads) void maxpool_kernel(PoolArgs a) {
                 }
             }
     }
+}
+
+// total channels of the pooled tensor, or -1: nseg outside 1..ISG_MAX_SEGS, an empty
+// segment, or more channels than the kernel's coefficient table in LDS holds
+int pool_channels(const isg_vtensor& x) {
+    if (x.nseg < 1 || x.nseg > ISG_MAX_SEGS) return -1;
+    int64_t C = 0;
+    for (int i = 0; i < x.nseg; ++i) {
+        if (x.s[i].C < 1) return -1;
+        C += x.s[i].C;
+    }
+    return C > ISG_MAX_CH ? -1 : (int)C;
+}
+
+// the forward's vector loads apply: k = 4 reads each window row as 16 B, k = 2 as 8 B, so
+// every segment's planes start on that boundary (W % k == 0 keeps the rows on it)
+bool pool_vec_ok(const isg_vtensor& x, int k) {
+    if (k != 2 && k != 4) return false;
+    for (int i = 0; i < x.nseg; ++i)
+        if (!al(x.s[i].p, 4 * k) || x.s[i].n_stride % k) return false;
+    return true;
 }
 
 // ---- BatchNorm running stats & gradient finalisation -------------------------------
@@ -974,8 +996,12 @@ extern "C" {
 int32_t isg_tail_fwd(const isg_tail* t, isg_stream_t st) {
     if ((t->H & 1) || (t->W & 1) || t->nterm < 1 || t->nterm > 3)
         return isg_set_error(ISG_ERR_UNSUPPORTED, "tail fwd: H, W must be even, 1..3 terms");
-    for (int i = 0; i < t->nterm; ++i)
+    for (int i = 0; i < t->nterm; ++i) {
         if (isg_seg_res(t->term[i])) return isg_set_error(ISG_ERR_UNSUPPORTED, "tail fwd: residual term form");
+        // the tail kernels load no saved output y: a BN_BWD term would be rebuilt with y = 0
+        if (t->term[i].xform == ISG_XF_BN_BWD)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "tail fwd: term %d is a BN_BWD segment", i);
+    }
     if (tail4_ok(*t, nullptr)) {
         dim3 grid4((unsigned)((((int64_t)t->H / 2) * (t->W / 4) + kThreads - 1) / kThreads), t->C, t->N);
         hipLaunchKernelGGL(tail_fwd4_kernel, grid4, dim3(kThreads), 0, st, *t);
@@ -990,8 +1016,15 @@ int32_t isg_tail_bwd(const isg_tail_grad* t, isg_stream_t st) {
     const isg_tail& f = t->f;
     if ((f.H & 1) || (f.W & 1) || f.nterm < 1 || f.nterm > 3)
         return isg_set_error(ISG_ERR_UNSUPPORTED, "tail bwd: H, W must be even, 1..3 terms");
-    for (int i = 0; i < f.nterm; ++i)
+    for (int i = 0; i < f.nterm; ++i) {
         if (isg_seg_res(f.term[i])) return isg_set_error(ISG_ERR_UNSUPPORTED, "tail bwd: residual term form");
+        if (f.term[i].xform == ISG_XF_BN_BWD)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "tail bwd: term %d is a BN_BWD segment", i);
+        // g is the gradient of the SUM: the kernels do not differentiate a term's own
+        // activation (the forward applies it)
+        if (f.term[i].xform == ISG_XF_BN_FWD && f.term[i].act != ISG_ACT_NONE)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "tail bwd: term %d has an activation of its own", i);
+    }
     // the kernels load every accumulating term's old value before any write:
     // two terms accumulating into one destination would lose one contribution
     for (int i = 0; i < f.nterm; ++i)
@@ -1012,10 +1045,11 @@ int32_t isg_maxpool_fwd(const isg_vtensor* x, int32_t k, float* out, int64_t out
                         isg_stream_t st) {
     if (k < 1 || x->H % k || x->W % k) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: H,W %% k");
     if (isg_vt_res(x)) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: residual input form");
-    int C = 0;
-    for (int i = 0; i < x->nseg; ++i) C += x->s[i].C;
+    const int C = pool_channels(*x);
+    if (C < 0) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: 1..%d segments, at most %d channels", ISG_MAX_SEGS, ISG_MAX_CH);
     PoolArgs a{};
     a.x = *x; a.k = k; a.out = out; a.out_n_stride = out_n_stride;
+    a.vec = pool_vec_ok(*x, k) ? 1 : 0;
     dim3 grid((unsigned)(((int64_t)(x->H / k) * (x->W / k) + kThreads - 1) / kThreads), C, x->N);
     hipLaunchKernelGGL(maxpool_kernel<false>, grid, dim3(kThreads), 0, st, a);
     return isg_check_launch("maxpool_kernel<fwd>");
@@ -1025,11 +1059,20 @@ int32_t isg_maxpool_bwd(const isg_vtensor* x, int32_t k, const float* dout, int6
                         const isg_sinks* dx, isg_stream_t st) {
     if (k < 1 || x->H % k || x->W % k) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: H,W %% k");
     if (isg_vt_res(x) || isg_sinks_res(dx)) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: residual form");
-    int C = 0;
-    for (int i = 0; i < x->nseg; ++i) C += x->s[i].C;
-    for (int i = 0; i < dx->nsink; ++i)
+    const int C = pool_channels(*x);
+    if (C < 0) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: 1..%d segments, at most %d channels", ISG_MAX_SEGS, ISG_MAX_CH);
+    // sink_of picks a sink by its c0 alone: the sinks must tile [0, C) in order
+    if (dx->nsink < 1 || dx->nsink > ISG_MAX_SEGS)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool bwd: 1..%d sinks", ISG_MAX_SEGS);
+    int cs = 0;
+    for (int i = 0; i < dx->nsink; ++i) {
         if (dx->s[i].mode == ISG_SINK_ACTBWD)
             return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool bwd: ACTBWD sink");
+        if (dx->s[i].c0 != cs || dx->s[i].C < 1 || dx->s[i].C > C - cs)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool bwd: the sinks do not cover channels [0, %d)", C);
+        cs += dx->s[i].C;
+    }
+    if (cs != C) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool bwd: the sinks do not cover channels [0, %d)", C);
     PoolArgs a{};
     a.x = *x; a.k = k; a.dout = dout; a.dout_n_stride = dout_n_stride; a.dx = *dx;
     dim3 grid((unsigned)(((int64_t)(x->H / k) * (x->W / k) + kThreads - 1) / kThreads), C, x->N);

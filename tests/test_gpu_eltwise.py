@@ -1,0 +1,584 @@
+"""The element-wise kernels of eltwise.hip (max-pool, residual tails, sigmoid + BCE, sigmoid,
+Adam, the fp64 fill) against plain references, straight through the C-ABI, at the shapes and
+operands where each takes another path: segment and sink selection, channel slices of wider
+buffers, partial last workgroups, the vector / scalar dispatch boundaries, NULL outputs and
+the host-side refusals. Inputs and references: tests/eltwise_cases.py (their properties are
+proved on the CPU by tests/test_eltwise_cases_cpu.py).
+
+Every output buffer starts as NaN (a canary for integer / double buffers); a kernel that
+writes a slice must leave every byte around it as it was."""
+import numpy as np
+import pytest
+import torch
+
+from instancesegmentation_amd import _lib as L
+from oracle import epilogue_oracle as E
+from tests import eltwise_cases as EC
+from tests.isg_helpers import (bn_spec_eval, bn_spec_train, call, ptr, rep_fold, rep_zeros, sinks,
+                               stream, struct, vt)
+from tests.test_gpu_kernels import close
+from tests.test_gpu_step_epilogue import report
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+N = EC.N
+NAN = float("nan")
+POISON = 1e30  # around the slice of an input: a misplaced read shows
+
+
+def dev(a):
+    return torch.from_numpy(np.array(a, order="C")).to(DEV)  # a copy: the cases are read-only
+
+
+def bits(t):
+    """The raw words of a float tensor as numpy (NaN compares as its bits)."""
+    t = t.detach().contiguous().cpu()
+    return t.view(torch.int64 if t.dtype == torch.float64 else torch.int32).numpy()
+
+
+def same_bits(got, want, what):
+    bad = int((bits(got) != bits(want)).sum())
+    assert bad == 0, f"{what}: {bad} elements differ bitwise"
+
+
+class Slab:
+    """A [N, C, H, W] channel slice at channel c0 of a wider [N, C + pad, H, W] buffer, which
+    starts `off` floats into its allocation. `data` fills the slice, `fill` everything else."""
+
+    def __init__(self, C, H, W, data=None, fill=NAN, pad=3, c0=2, off=0):
+        self.C, self.c0 = C, c0
+        self.flat = torch.full((off + N * (C + pad) * H * W,), fill, dtype=torch.float32, device=DEV)
+        self.buf = self.flat[off:].view(N, C + pad, H, W)
+        if data is not None:
+            self.buf[:, c0:c0 + C] = dev(np.asarray(data, np.float32))
+        self.n_stride = (C + pad) * H * W
+        self.ptr = self.buf[0, c0].data_ptr()
+        self.before = self.flat.clone()
+
+    def get(self):
+        return self.buf[:, self.c0:self.c0 + self.C]
+
+    def outside_untouched(self, what, whole=False):
+        changed = torch.from_numpy(bits(self.flat) != bits(self.before))
+        if not whole:
+            inside = torch.zeros_like(self.buf, dtype=torch.bool)
+            inside[:, self.c0:self.c0 + self.C] = True
+            off = self.flat.numel() - inside.numel()
+            changed[off:] &= ~inside.reshape(-1).cpu()
+        assert not changed.any(), f"{what}: {int(changed.sum())} words around the slice changed"
+
+
+def rep_spread(vals):
+    """A replicated accumulator whose replicas sum to `vals` (dyadic shares: to within an fp64
+    rounding), so a consumer that read replica 0 alone would be off by half."""
+    vals = np.asarray(vals, np.float64)
+    w = [2.0 ** -(r + 1) for r in range(L.STAT_REP - 1)]
+    w.append(1.0 - sum(w))
+    return dev(np.concatenate([wi * vals for wi in w]))
+
+
+def seg_spec(sg, slab, keep, H, W):
+    """The isg_vseg of a case segment read from `slab`."""
+    s = {"p": slab.ptr, "n_stride": slab.n_stride, "C": sg["C"]}
+    kind = sg["kind"]
+    if kind == "plain":
+        s["xform"] = L.XF_PLAIN
+        return s
+    s.update(xform=L.XF_BN_FWD, act=L.ACT[sg.get("act", "none")])
+    if sg.get("act") == "prelu":
+        SL = dev(sg["slope"])
+        keep.append(SL)
+        s["slope"] = ptr(SL)
+    if kind == "act_only":
+        s["bn"] = {"train": 1}  # no statistics: the activation alone
+        return s
+    GA, BE = dev(sg["gamma"]), dev(sg["beta"])
+    keep += [GA, BE]
+    if kind == "bn_eval":
+        RM, RV = dev(sg["rm"]), dev(sg["rv"])
+        ST = rep_zeros(4 * sg["C"])
+        keep += [RM, RV, ST]
+        s["bn"] = dict(bn_spec_eval(GA, BE, RM, RV), stats=ptr(ST))
+    elif kind == "bn_train":
+        ST = rep_spread(sg["stats"])
+        keep.append(ST)
+        s["bn"] = bn_spec_train(GA, BE, ST, sg["count"])
+    else:  # "coef": finalised coefficients; statistics, gamma and beta hold NaN
+        CO = dev(EC.coef_block(sg).reshape(-1))
+        ST = torch.full((L.STAT_REP * 4 * sg["C"],), NAN, dtype=torch.float64, device=DEV)
+        GA.fill_(NAN)
+        BE.fill_(NAN)
+        keep += [CO, ST]
+        s["bn"] = dict(bn_spec_train(GA, BE, ST, sg["count"]), coef=ptr(CO))
+    s["stats_buf"] = ST
+    return s
+
+
+def strip(spec):
+    return {k: v for k, v in spec.items() if k != "stats_buf"}
+
+
+# ---- max-pool ------------------------------------------------------------------------------
+POOL_ALL = [(s, False) for s in EC.POOL_SHAPES] + [(s, True) for s in EC.POOL_SMALL_SHAPES]
+POOL_IDS = [f"{h}x{w}_k{k}{'_small' if sm else ''}" for (h, w, k), sm in POOL_ALL]
+
+
+def pool_input(case, off=0):
+    keep, slabs, segs = [], [], []
+    for sg in case["segs"]:
+        # wide enough that a kernel which picked the wrong segment base reads POISON
+        sl = Slab(sg["C"], case["H"], case["W"], data=sg["x"], fill=POISON, pad=12, c0=1, off=off)
+        slabs.append(sl)
+        segs.append(strip(seg_spec(sg, sl, keep, case["H"], case["W"])))
+    return vt(segs, N, case["H"], case["W"]), keep, slabs
+
+
+def pool_forward(case, off=0):
+    H, W, k, C = case["H"], case["W"], case["k"], case["C"]
+    xs, keep, slabs = pool_input(case, off)
+    out = Slab(C, H // k, W // k, pad=16 - C, c0=2)
+    call("isg_maxpool_fwd", xs, k, out.ptr, out.n_stride, stream())
+    out.outside_untouched("maxpool out")
+    for sl in slabs:
+        sl.outside_untouched("maxpool input", whole=True)
+    return out.get().cpu()
+
+
+@pytest.mark.parametrize("shape,small", POOL_ALL, ids=POOL_IDS)
+def test_maxpool_fwd_segments(shape, small):
+    case = EC.pool_case(*shape, small=small)
+    got = pool_forward(case)
+    ref, _ = EC.pool_forward_ref(case)
+    for sg in case["segs"]:
+        c = slice(sg["c0"], sg["c0"] + sg["C"])
+        if sg["kind"] == "plain":  # a selection of input values: exact, NaN and -inf included
+            assert np.array_equal(got[:, c].numpy(), ref[:, c].float().numpy(), equal_nan=True)
+        else:
+            close(got[:, c], ref[:, c], what=f"maxpool {sg['kind']}+{sg['act']}")
+
+
+@pytest.mark.parametrize("shape,small", [(EC.POOL_SHAPES[0], False), (EC.POOL_SHAPES[1], False),
+                                         (EC.POOL_SMALL_SHAPES[1], True)],
+                         ids=["40x36_k2", "40x36_k4", "12x24_k4_small"])
+def test_maxpool_fwd_misaligned_operand_takes_the_generic_path(shape, small):
+    """Every segment's p 4 bytes off a 16-B boundary: pixel by pixel, same values."""
+    case = EC.pool_case(*shape, small=small)
+    same_bits(pool_forward(case, off=1), pool_forward(case), "maxpool fwd, p + 4 B")
+
+
+@pytest.mark.parametrize("modes", ["store+accum", "none+store", "accum+none"])
+@pytest.mark.parametrize("shape,small", POOL_ALL, ids=POOL_IDS)
+def test_maxpool_bwd_sinks(shape, small, modes):
+    """Two sinks split inside a segment. Bit for bit torch's routing: STORE writes zeros off
+    the argmax, ACCUM changes the argmax alone, NONE (a NULL pointer) writes nothing."""
+    case = EC.pool_case(*shape, small=small)
+    H, W, k, C = case["H"], case["W"], case["k"], case["C"]
+    split = 5 if not small else 3
+    assert split not in [sg["c0"] for sg in case["segs"]]
+    rng = np.random.default_rng(17)
+    dout = rng.normal(0.0, 1.0, (N, C, H // k, W // k)).astype(np.float32)
+    dx, hit = EC.pool_backward_ref(case, dout)
+    xs, keep, _ = pool_input(case)
+    DO = Slab(C, H // k, W // k, data=dout, fill=POISON)
+    lst, slabs, want = [], [], []
+    for (c0, c1), mode in zip(((0, split), (split, C)), modes.split("+")):
+        if mode == "none":
+            lst.append({"c0": c0, "C": c1 - c0, "mode": L.SINK_NONE})
+            continue
+        old = rng.normal(0.0, 1.0, (N, c1 - c0, H, W)).astype(np.float32)
+        sl = Slab(c1 - c0, H, W, data=old if mode == "accum" else None)
+        lst.append({"p": sl.ptr, "n_stride": sl.n_stride, "c0": c0, "C": c1 - c0,
+                    "mode": L.SINK_ACCUM if mode == "accum" else L.SINK_STORE})
+        d, h = dx[:, c0:c1], hit[:, c0:c1]
+        slabs.append(sl)
+        want.append(np.where(h & (d != 0), old + d, old) if mode == "accum" else d)
+    call("isg_maxpool_bwd", xs, k, DO.ptr, DO.n_stride, sinks(lst), stream())
+    for sl, w in zip(slabs, want):
+        same_bits(sl.get(), torch.from_numpy(np.ascontiguousarray(w)), f"maxpool bwd {modes}")
+        sl.outside_untouched("maxpool bwd sink")
+    DO.outside_untouched("maxpool dout", whole=True)
+
+
+def test_maxpool_refusals():
+    """Refused on the host, before any launch: the buffers are real but far too small for
+    what the arguments describe."""
+    X = torch.zeros(N * 4 * 4, device=DEV)
+    Y = torch.full((N * 4,), NAN, device=DEV)
+    DX = torch.full((N * 4 * 4,), NAN, device=DEV)
+    seg = lambda C: {"p": ptr(X), "n_stride": 16, "C": C, "xform": L.XF_PLAIN}
+    sk = lambda c0, C: {"p": ptr(DX), "n_stride": 16, "c0": c0, "C": C, "mode": L.SINK_STORE}
+    bad_x = {"more than ISG_MAX_CH channels": vt([seg(300), seg(213)], N, 2, 2),
+             "nseg 0": vt([], N, 2, 2),
+             "nseg 4": struct(L.VTensor, {"s": [seg(1)] * 3, "nseg": 4, "N": N, "H": 2, "W": 2})}
+    for what, xs in bad_x.items():
+        with pytest.raises(RuntimeError, match=r"\(-2\)"):
+            call("isg_maxpool_fwd", xs, 2, ptr(Y), 4, stream())
+        with pytest.raises(RuntimeError, match=r"\(-2\)"):
+            call("isg_maxpool_bwd", xs, 2, ptr(Y), 4, sinks([sk(0, 4)]), stream())
+    ok = vt([seg(2), seg(2)], N, 2, 2)
+    bad_sinks = {"a gap": [sk(0, 2), sk(3, 1)], "short": [sk(0, 3)], "long": [sk(0, 5)],
+                 "not from 0": [sk(1, 3)], "overlap": [sk(0, 3), sk(2, 2)], "no sink": []}
+    for what, lst in bad_sinks.items():
+        with pytest.raises(RuntimeError, match=r"\(-2\)"):
+            call("isg_maxpool_bwd", ok, 2, ptr(Y), 4, sinks(lst), stream())
+    torch.cuda.synchronize()
+    assert torch.isnan(Y).all() and torch.isnan(DX).all()
+
+
+def test_maxpool_full_channel_table():
+    """Exactly ISG_MAX_CH channels (300 + 212) are accepted and every one is pooled."""
+    x = np.random.default_rng(3).normal(0.0, 1.0, (N, 512, 2, 2)).astype(np.float32)
+    X = dev(x)
+    Y = torch.full((N, 512 + 1), NAN, device=DEV)
+    segs = [{"p": ptr(X), "n_stride": 2048, "C": 300, "xform": L.XF_PLAIN},
+            {"p": X[0, 300].data_ptr(), "n_stride": 2048, "C": 212, "xform": L.XF_PLAIN}]
+    call("isg_maxpool_fwd", vt(segs, N, 2, 2), 2, ptr(Y), 513, stream())
+    assert torch.isnan(Y[:, 512]).all()
+    assert np.array_equal(Y[:, :512].cpu().numpy(), x.max((2, 3)))
+
+
+# ---- residual tails ------------------------------------------------------------------------
+TAIL_SHAPES = [(H, W, False) for H, W in EC.TAIL_SHAPES] + [(128, 128, True)]
+TAIL_IDS = [f"{h}x{w}{'_off8' if o else ''}" for h, w, o in TAIL_SHAPES]
+TAIL_RUNS = [(f, a) for f in ("a", "b", "c") for a in ("prelu", "relu", "none")] + \
+    [("c_null", "prelu"), ("d", "prelu")]
+
+
+class TailRun:
+    """One isg_tail_fwd and one isg_tail_bwd of a case, every operand a channel slice."""
+
+    def __init__(self, case, off8=False, coef=False, g_null=False, sg_null=False):
+        H, W, C = case["H"], case["W"], case["C"]
+        self.case, self.keep, self.terms = case, [], []
+        specs, ups = [], []
+        for tm in case["terms"]:
+            h, w = (H // 2, W // 2) if tm["up"] else (H, W)
+            sl = Slab(C, h, w, data=tm["x"], fill=POISON, c0=1)
+            sp = seg_spec(tm, sl, self.keep, h, w)
+            if coef and tm["kind"] != "plain":
+                CO = torch.full((8 * C,), NAN, device=DEV)
+                self.keep.append(CO)
+                sp["bn"]["coef"] = ptr(CO)
+                call("isg_bn_finalize", struct(L.Bn, sp["bn"]), 1, 0, stream())
+            self.terms.append((sl, sp))
+            specs.append(strip(sp))
+            ups.append(1 if tm["up"] else 0)
+        SL = dev(case["slope"])
+        self.keep.append(SL)
+        self.out = Slab(C, H, W, off=2 if off8 else 0)
+        t = {"term": specs, "up": ups + [0] * (3 - len(ups)), "nterm": len(specs),
+             "act": L.ACT[case["act"]], "slope": ptr(SL), "N": N, "C": C, "H": H, "W": W,
+             "out": self.out.ptr, "out_n_stride": self.out.n_stride}
+        call("isg_tail_fwd", struct(L.Tail, t), stream())
+        self.out.outside_untouched("tail out")
+        # backward
+        self.stats0 = [None if tm["kind"] == "plain" else sp["stats_buf"].clone()
+                       for tm, (_, sp) in zip(case["terms"], self.terms)]
+        self.dout = Slab(C, H, W, data=case["dout"], fill=POISON, off=2 if off8 else 0)
+        self.g = None if g_null else Slab(C, H, W, c0=0)
+        self.sg = None if sg_null else rep_zeros(C)
+        self.dterm = []
+        for tm in case["terms"]:
+            h, w = (H // 2, W // 2) if tm["up"] else (H, W)
+            self.dterm.append(None if tm["dterm"] is None else
+                              Slab(C, h, w, data=tm.get("old"), c0=3))
+        pad3 = lambda l, z: l + [z] * (3 - len(l))
+        tg = {"f": t, "dout": self.dout.ptr, "dout_n_stride": self.dout.n_stride,
+              "g": self.g.ptr if self.g else None, "g_n_stride": self.g.n_stride if self.g else 0,
+              "dterm": pad3([d.ptr if d else None for d in self.dterm], None),
+              "dterm_n_stride": pad3([d.n_stride if d else 0 for d in self.dterm], 0),
+              "dterm_accum": pad3([1 if tm["dterm"] == "accum" else 0 for tm in case["terms"]], 0),
+              "slope_grad": ptr(self.sg)}
+        call("isg_tail_bwd", struct(L.TailGrad, tg), stream())
+        for sl in [self.out, self.g] + self.dterm:
+            if sl is not None:
+                sl.outside_untouched("tail bwd output")
+        for sl in [self.dout] + [s for s, _ in self.terms]:
+            sl.outside_untouched("tail input", whole=True)
+
+    def stats(self, i):
+        """(gsum, gxsum) the backward left in term i's statistics block; its forward half
+        (sum, sumsq) must be what went in, bit for bit in every replica."""
+        C = self.case["C"]
+        ST = self.terms[i][1]["stats_buf"]
+        same_bits(ST.view(L.STAT_REP, 4 * C)[:, :2 * C], self.stats0[i].view(L.STAT_REP, 4 * C)[:, :2 * C],
+                  "sum / sumsq after the backward")
+        st = rep_fold(ST, 4 * C).cpu().numpy()
+        return st[2 * C:3 * C], st[3 * C:]
+
+    def check(self, ref, fwd=True):
+        case = self.case
+        T = torch.from_numpy
+        if fwd:
+            close(self.out.get(), T(ref["out"]), what="tail out")
+        if self.g is not None:
+            close(self.g.get(), T(ref["g"]), what="tail g")
+        for i, tm in enumerate(case["terms"]):
+            if tm["kind"] == "plain":
+                if self.dterm[i] is not None:
+                    close(self.dterm[i].get(), T(ref["dterm"][i]), what=f"tail dterm {i}")
+            else:
+                gs, gxs = self.stats(i)
+                close(T(gs), T(ref["gsum"][i]), what=f"tail gsum of term {i}")
+                close(T(gxs), T(ref["gxsum"][i]), what=f"tail gxsum of term {i}")
+        if case["act"] == "prelu" and self.sg is not None:
+            close(rep_fold(self.sg, case["C"]), T(ref["slope_grad"]), what="tail slope_grad")
+
+
+@pytest.mark.parametrize("form,act", TAIL_RUNS, ids=[f"{f}-{a}" for f, a in TAIL_RUNS])
+@pytest.mark.parametrize("H,W,off8", TAIL_SHAPES, ids=TAIL_IDS)
+def test_tail_forms(form, act, H, W, off8):
+    """Forward and backward of every term form at every dispatch boundary, against the fp64
+    reference: the same result whichever kernel form ran."""
+    case = EC.tail_case(form, act, H, W)
+    TailRun(case, off8=off8).check(EC.tail_ref(case))
+
+
+@pytest.mark.parametrize("H,W,off8", TAIL_SHAPES, ids=TAIL_IDS)
+def test_tail_finalised_coef_is_bitwise_the_statistics_path(H, W, off8):
+    case = EC.tail_case("a", "prelu", H, W)
+    a, b = TailRun(case, off8=off8), TailRun(case, off8=off8, coef=True)
+    same_bits(b.out.get(), a.out.get(), "tail out, coef vs statistics")
+    same_bits(b.g.get(), a.g.get(), "tail g, coef vs statistics")
+    b.check(EC.tail_ref(case))
+
+
+@pytest.mark.parametrize("H,W,off8", TAIL_SHAPES, ids=TAIL_IDS)
+def test_tail_null_g_and_null_slope_grad(H, W, off8):
+    case = EC.tail_case("c", "prelu", H, W)
+    ref = EC.tail_ref(case)
+    full = TailRun(case, off8=off8)
+    for kw in ({"g_null": True}, {"sg_null": True}, {"g_null": True, "sg_null": True}):
+        r = TailRun(case, off8=off8, **kw)
+        r.check(ref)
+        for i in (1, 2):
+            same_bits(r.dterm[i].get(), full.dterm[i].get(), f"tail dterm {i} with {kw}")
+        if r.g is not None:
+            same_bits(r.g.get(), full.g.get(), f"tail g with {kw}")
+
+
+def test_tail_fwd_honours_a_terms_own_activation():
+    """A BN_FWD term with an activation of its own: the forward applies it (the backward
+    refuses the form, test_tail_refusals)."""
+    case = EC.tail_case("b", "none", 40, 36)
+    tm = dict(case["terms"][0], act="relu")
+    mod = dict(case, terms=[tm, case["terms"][1]])
+    C, H, W = case["C"], 40, 36
+    keep = []
+    slabs = [Slab(C, H, W, data=t["x"], fill=POISON, c0=1) for t in mod["terms"]]
+    specs = [strip(seg_spec(t, s, keep, H, W)) for t, s in zip(mod["terms"], slabs)]
+    out = Slab(C, H, W)
+    call("isg_tail_fwd", struct(L.Tail, {"term": specs, "up": [0, 0, 0], "nterm": 2, "act": 0,
+                                         "N": N, "C": C, "H": H, "W": W, "out": out.ptr,
+                                         "out_n_stride": out.n_stride}), stream())
+    close(out.get(), torch.from_numpy(EC.tail_pre64(mod)), what="tail fwd, term relu")
+    assert not np.allclose(EC.tail_pre64(mod), EC.tail_pre64(case))
+
+
+def test_tail_refusals():
+    C, H, W = 2, 4, 4
+    X = torch.zeros(N * C * H * W, device=DEV)
+    O = torch.full((N * C * H * W,), NAN, device=DEV)
+    D = torch.full((N * C * H * W,), NAN, device=DEV)
+    GA = torch.ones(C, device=DEV)
+    ST = rep_zeros(4 * C)
+    ns = C * H * W
+    plain = {"p": ptr(X), "n_stride": ns, "C": C, "xform": L.XF_PLAIN}
+    bn = lambda xf, act: {"p": ptr(X), "n_stride": ns, "C": C, "xform": xf, "act": act,
+                          "bn": bn_spec_train(GA, GA, ST, N * H * W)}
+
+    def tail(terms, h=H, w=W, nterm=None):
+        return {"term": terms[:3], "up": [0, 0, 0], "nterm": len(terms) if nterm is None else nterm,
+                "act": 0, "N": N, "C": C, "H": h, "W": w, "out": ptr(O), "out_n_stride": ns}
+
+    def grad(t, dterm=(None, None, None), accum=(0, 0, 0)):
+        return {"f": t, "dout": ptr(X), "dout_n_stride": ns, "g": ptr(D), "g_n_stride": ns,
+                "dterm": list(dterm), "dterm_n_stride": [ns] * 3, "dterm_accum": list(accum)}
+
+    both = {"odd H": tail([plain], h=3), "odd W": tail([plain], w=3),
+            "nterm 0": tail([], nterm=0), "nterm 4": tail([plain] * 3, nterm=4),
+            "a BN_BWD term": tail([plain, bn(L.XF_BN_BWD, 0)])}
+    for what, t in both.items():
+        with pytest.raises(RuntimeError, match=r"\(-2\)"):
+            call("isg_tail_fwd", struct(L.Tail, t), stream())
+        with pytest.raises(RuntimeError, match=r"\(-2\)"):
+            call("isg_tail_bwd", struct(L.TailGrad, grad(t)), stream())
+    for act in (L.ACT["relu"], L.ACT["prelu"]):
+        with pytest.raises(RuntimeError, match=r"\(-2\).*activation"):
+            call("isg_tail_bwd", struct(L.TailGrad, grad(tail([bn(L.XF_BN_FWD, act), plain]))), stream())
+    for accum in ((0, 1, 0), (1, 0, 0), (1, 1, 0)):
+        with pytest.raises(RuntimeError, match=r"\(-1\).*share"):
+            call("isg_tail_bwd", struct(L.TailGrad, grad(tail([plain, plain]), (ptr(D), ptr(D), None),
+                                                         accum)), stream())
+    torch.cuda.synchronize()
+    assert torch.isnan(O).all() and torch.isnan(D).all() and not ST.any()
+
+
+# ---- sigmoid + BCE -------------------------------------------------------------------------
+def run_bce(x, t, grad_scale, off=0, dl=True, acc0=0.0):
+    """isg_bce_sigmoid on copies of x, t that start `off` floats past a 16-B boundary:
+    (loss accumulator after the call, dlogits or the untouched canary buffer)."""
+    n = x.size
+    X, T = torch.zeros(n + off + 4, device=DEV), torch.zeros(n + off + 4, device=DEV)
+    X[off:off + n], T[off:off + n] = dev(x), dev(t)
+    G = torch.full((n + off + 4,), NAN, device=DEV)
+    acc = torch.full((3,), 7.0, dtype=torch.float64, device=DEV)
+    acc[1] = acc0
+    a0 = acc.data_ptr() + 8
+    call("isg_bce_sigmoid", X.data_ptr() + 4 * off, T.data_ptr() + 4 * off, n, a0,
+         G.data_ptr() + 4 * off if dl else None, grad_scale, stream())
+    assert acc[0].item() == 7.0 and acc[2].item() == 7.0
+    assert torch.isnan(G[:off]).all() and torch.isnan(G[off + n:]).all()
+    if not dl:
+        assert torch.isnan(G).all(), "dlogits == NULL, yet the canary buffer changed"
+    assert np.array_equal(X[off:off + n].cpu().numpy(), x) and np.array_equal(
+        T[off:off + n].cpu().numpy(), t)
+    return acc[1].item(), G[off:off + n].cpu().numpy()
+
+
+def bce_compare(what, x, t, planted, grad_scale, loss, dl):
+    """The bars of test_bce_matches_golden: loss 1e-6 relative, dlogits 1e-6 max|ref| + 1e-12
+    per element; planted saturated elements equal."""
+    ref_loss, ref_dl = EC.bce_ref(x, t, grad_scale)
+    bar = 1e-6 * np.abs(ref_dl).max() + 1e-12
+    worst = {"loss": abs(loss - ref_loss) / (1e-6 * max(1.0, abs(ref_loss))),
+             "dlogits": float((np.abs(dl.astype(np.float64) - ref_dl) / bar).max())}
+    uneq = planted & (dl != ref_dl)
+    print(f"{what}: planted elements differing from torch {int(uneq.sum())} of {int(planted.sum())}"
+          + "".join(f"; x={x[i]} t={t[i]}: {dl[i]!r} vs {ref_dl[i]!r}" for i in np.flatnonzero(uneq)[:6]))
+    report(what, worst)
+    assert not uneq.any(), "a planted saturated element differs from torch"
+
+
+@pytest.mark.parametrize("scale", ["1/n", "1", "0.37"])
+@pytest.mark.parametrize("n", EC.BCE_VEC_N + EC.BCE_SCALAR_N)
+def test_bce_lengths(n, scale):
+    x, t, planted = EC.bce_inputs(n)
+    gs = {"1/n": 1.0 / n, "1": 1.0, "0.37": 0.37}[scale]
+    loss, dl = run_bce(x, t, gs)
+    bce_compare(f"bce n={n} grad_scale={scale}", x, t, planted, gs, loss, dl)
+
+
+def test_bce_vector_and_scalar_kernels_agree_bitwise():
+    """8192 elements 16-B aligned (the quad kernel) and 4 bytes off (the scalar one): the
+    same arithmetic with contraction off, so the same dlogits; both against the reference."""
+    x, t, planted = EC.bce_inputs(8192)
+    la, da = run_bce(x, t, 0.37)
+    lb, db = run_bce(x, t, 0.37, off=1)
+    bce_compare("bce n=8192 at +4 B (scalar kernel)", x, t, planted, 0.37, lb, db)
+    same_bits(torch.from_numpy(da), torch.from_numpy(db), "dlogits, quad vs scalar kernel")
+    assert abs(la - lb) <= 1e-12 * abs(la)  # fp64 sums of the same fp32 terms, another order
+
+
+@pytest.mark.parametrize("n,off", [(8196, 0), (8193, 0), (8192, 1)], ids=["quad", "scalar", "scalar_off4"])
+def test_bce_null_dlogits_and_running_accumulator(n, off):
+    x, t, _ = EC.bce_inputs(n)
+    full, _ = run_bce(x, t, 1.0 / n, off=off)
+    nodl, _ = run_bce(x, t, 1.0 / n, off=off, dl=False)
+    assert abs(nodl - full) <= 1e-12 * abs(full)
+    added, _ = run_bce(x, t, 1.0 / n, off=off, acc0=12345.5)
+    assert abs((added - 12345.5) - full) <= 1e-6 * abs(full), "loss_acc is added to"
+
+
+def test_bce_golden_padded_onto_the_vector_path(golden_dir):
+    """The golden fixture (282 elements, scalar kernel) padded to 284 = 71 quads with two
+    elements whose loss is known (logit 0, target 0.5: ln 2 each)."""
+    z = np.load(f"{golden_dir}/bce.npz")
+    n0 = z["logits"].size
+    assert n0 == 282
+    x = np.concatenate([z["logits"], np.zeros(2, np.float32)])
+    t = np.concatenate([z["target"], np.full(2, 0.5, np.float32)])
+    acc, dl = run_bce(x, t, 1.0 / n0)
+    pad = 2.0 * float(-np.log(np.float32(0.5)))
+    assert abs((acc - pad) / n0 - float(z["loss"])) < 1e-6 * max(1, abs(float(z["loss"])))
+    ref = z["dlogits"].astype(np.float64)
+    assert np.abs(dl[:n0] - ref).max() < 1e-6 * np.abs(ref).max() + 1e-12
+    sat = (z["logits"] >= 17) & (z["target"] == 0)
+    assert sat.any() and (dl[:n0][sat] == z["dlogits"][sat]).all()
+    assert (dl[n0:] == 0).all()  # p = t = 0.5
+
+
+# ---- sigmoid -------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", EC.SIGMOID_N)
+def test_sigmoid_fwd(n):
+    x, planted = EC.sigmoid_inputs(n)
+    X = dev(x)
+    Y = torch.full((n + 8,), NAN, device=DEV)
+    call("isg_sigmoid_fwd", ptr(X), ptr(Y), n, stream())
+    assert torch.isnan(Y[n:]).all()
+    got = Y[:n].cpu().numpy()
+    ref = EC.sigmoid_ref64(x)
+    assert (got[planted] == ref[planted].astype(np.float32)).all(), "exact 0 / 1 at +-120 and +-inf"
+    live = ~planted
+    bar = 2.0 ** -22 * np.abs(ref[live])  # one ulp of expf, relative, plus two roundings
+    cpu = torch.sigmoid(torch.from_numpy(x)).numpy()
+    print(f"sigmoid n={n}: worst |err| / bar of torch's CPU fp32 sigmoid on the same inputs "
+          f"{float((np.abs(cpu[live] - ref[live]) / bar).max()):.3g}")
+    report(f"sigmoid n={n}", {"kernel": float((np.abs(got[live] - ref[live]) / bar).max())})
+
+
+@pytest.mark.parametrize("n", EC.SIGMOID_N)
+def test_sigmoid_bwd(n):
+    y, dy = EC.sigmoid_bwd_inputs(n)
+    DX = torch.full((n + 8,), NAN, device=DEV)
+    Y, DY = dev(y), dev(dy)
+    call("isg_sigmoid_bwd", ptr(Y), ptr(DY), ptr(DX), n, stream())
+    assert torch.isnan(DX[n:]).all()
+    want = (dy * (np.float32(1.0) - y)) * y
+    assert want.dtype == np.float32
+    same_bits(DX[:n], torch.from_numpy(want), "sigmoid bwd")
+
+
+# ---- Adam ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("masked", [False, True], ids=["all", "mask10"])
+@pytest.mark.parametrize("wd", [0.0, EC.ADAM_WD])
+@pytest.mark.parametrize("step", [1, 2, 1000])
+@pytest.mark.parametrize("n", EC.ADAM_N)
+def test_adam(n, step, wd, masked):
+    p, g, m, v, live = EC.adam_inputs(n, step, masked)
+    P, G, M, V = dev(p), dev(g), dev(m), dev(v)
+    LV = dev(live) if masked else None
+    call("isg_adam", ptr(P), ptr(G), ptr(M), ptr(V), ptr(LV), n, step, 1e-3, 0.9, 0.999, 1e-8,
+         wd, stream())
+    got = [a.cpu().numpy() for a in (P, M, V)]
+    on = live.astype(bool) if masked else np.ones(n, bool)
+    for a, a0, what in zip(got, (p, m, v), ("param", "exp_avg", "exp_avg_sq")):
+        assert (a.view(np.uint32)[~on] == a0.view(np.uint32)[~on]).all(), f"masked {what} changed"
+    assert torch.equal(G.cpu(), torch.from_numpy(g))
+    rp, rm, rv = E.adam_step(p, g, m, v, step, 1e-3, 0.9, 0.999, 1e-8, wd)
+    p64, g64 = p.astype(np.float64), g.astype(np.float64)
+    ga = np.abs(g64) + wd * np.abs(p64)     # size of the operands of ge = g + wd*p
+    dge = 2.0 ** -23 * ga                   # its fp32 error: the product's and the sum's rounding
+    # param: the bar test_step_tail_matches_separate_calls_and_oracle applies to its Adam
+    # output (rtol 2e-6, atol 1e-9). The moments: the same 2e-6 (a dozen fp32 roundings, the
+    # kernel has four per moment), relative to the operands of the sums that may cancel:
+    # g, wd*p and m for exp_avg; for exp_avg_sq, a sum of positive terms, relative to the
+    # result plus what the rounding of ge contributes through (1 - beta2) ge^2
+    bars = {"param": 2e-6 * np.abs(rp) + 1e-9,
+            "exp_avg": 2e-6 * (ga + np.abs(m.astype(np.float64))) + 1e-30,
+            "exp_avg_sq": 2e-6 * np.abs(rv) + 1e-3 * (2 * np.abs(g64 + wd * p64) * dge + dge * dge) + 1e-30}
+    worst = {k: float((np.abs(a.astype(np.float64) - r)[on] / bars[k][on]).max()) if on.any() else 0.0
+             for k, a, r in zip(bars, got, (rp, rm, rv))}
+    report(f"adam n={n} step={step} wd={wd} {'mask' if masked else 'all'}", worst)
+
+
+def test_adam_refuses_step_below_one():
+    P = torch.full((4,), 2.0, device=DEV)
+    for step in (0, -3):
+        with pytest.raises(RuntimeError, match=r"\(-1\)"):
+            call("isg_adam", ptr(P), ptr(P), ptr(P), ptr(P), None, 4, step, 1e-3, 0.9, 0.999, 1e-8,
+                 0.0, stream())
+    torch.cuda.synchronize()
+    assert (P == 2.0).all()
+
+
+# ---- fp64 fill -----------------------------------------------------------------------------
+@pytest.mark.parametrize("value", [0.0, -0.0, 1.5])
+@pytest.mark.parametrize("n", [0, 1, 257, 2048 * 256 + 3])
+def test_fill_f64(n, value):
+    canary = -12345.678
+    B = torch.full((n + 5,), canary, dtype=torch.float64, device=DEV)
+    call("isg_fill_f64", ptr(B), n, value, stream())
+    want = torch.full((n + 5,), canary, dtype=torch.float64)
+    want[:n] = value
+    same_bits(B, want, f"fill n={n} value={value!r}")
