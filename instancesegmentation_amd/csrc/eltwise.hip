@@ -9,6 +9,7 @@
 //  * fused sigmoid + BCELoss (segment.py:534, train_instance.py:299,378);
 //  * Adam (train_instance.py:297,380).
 #include <cstring>
+#include <type_traits>
 
 #include "common.h"
 
@@ -48,9 +49,91 @@ ISG_DEV void block_reduce(float (&v)[NV], float* sh) {
 }
 
 // ---- residual tail ----------------------------------------------------------------
-// Thread unit: a 2x2 pixel quad of one (n, c) plane (H, W are even in this network:
-// input sides are multiples of 16), so an x2-upsampled term is one
-// low-resolution value per thread and its gradient is the quad's sum.
+// Thread unit: two rows of PX pixels of one (n, c) plane (H, W are even in this network:
+// input sides are multiples of 16), so an x2-upsampled term is PX/2
+// low-resolution values per thread and its gradient is the sum of each one's 2x2 block.
+//  PX = 2  any even H, W: 8-B accesses, the upsampled term a scalar;
+//  PX = 4  W % 4 == 0 and 16-B aligned planes (tail4_ok): every full-resolution operand
+//          moves as 16-B accesses, the upsampled term as one 8-B pair; half the threads,
+//          workgroups and reductions of PX = 2.
+// The forward is one body for both widths: every loop over PX is unrolled by its pragma (the
+// library builds with -fno-unroll-loops). It indexes units in int, pixels in int64: the host
+// refuses a plane whose PX = 2 units do not fit an int (tail_check). The backward is still
+// two hand-written kernels (below).
+template <int V>
+using tvec = float __attribute__((ext_vector_type(V)));
+template <int V>
+ISG_DEV tvec<V> tail_ld(const float* p, int64_t i) {
+    return *(const tvec<V> __attribute__((address_space(1)))*)((gcfloat_p)p + i);
+}
+template <int V>
+ISG_DEV void tail_st(float* p, int64_t i, tvec<V> v) {
+    *(tvec<V> __attribute__((address_space(1)))*)((gfloat_p)p + i) = v;
+}
+
+// the raw values of term `tm` at pixels (y, x .. x + PX - 1) of plane (n, c)
+template <int PX>
+ISG_DEV tvec<PX> tail_term(const isg_vseg& tm, int up, int n, int c, int H, int W, int y, int x) {
+    if (up) {
+        const int w2 = W >> 1;
+        const int64_t off = (int64_t)n * tm.n_stride + (int64_t)c * (H >> 1) * w2 + (int64_t)(y >> 1) * w2 + (x >> 1);
+        const tvec<PX / 2> v = tail_ld<PX / 2>(tm.p, off);
+        tvec<PX> r;
+#pragma unroll
+        for (int e = 0; e < PX; ++e) r[e] = v[e >> 1];
+        return r;
+    }
+    return tail_ld<PX>(tm.p, (int64_t)n * tm.n_stride + (int64_t)c * H * W + (int64_t)y * W + x);
+}
+
+template <int PX>
+__global__ __launch_bounds__(kThreads) void tail_fwd_kernel(isg_tail t) {
+    const int c = blockIdx.y, n = blockIdx.z;
+    const int H = t.H, W = t.W;
+    const int qw = W / PX;
+    const int nq = (H >> 1) * qw;
+    const int q = blockIdx.x * kThreads + threadIdx.x;
+    if (q >= nq) return;
+    const int qy = q / qw, x0 = (q - qy * qw) * PX;
+    // the unit's raw term values first: their loads do not depend on the coefficients
+    // (consumer-side BatchNorm finalisation reads the statistics below), so both round
+    // trips overlap instead of running back to back
+    tvec<PX> raw[2][3];
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            raw[dy][i] = tvec<PX>(0.f);
+            if (i < t.nterm) raw[dy][i] = tail_term<PX>(t.term[i], t.up[i], n, c, H, W, 2 * qy + dy, x0);
+        }
+    ChanCoef k[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        if (i < t.nterm) k[i] = seg_coef(t.term[i], c);
+    const float slope = (t.act == ISG_ACT_PRELU) ? t.slope[c] : 0.f;
+    float* out = t.out + (int64_t)n * t.out_n_stride + (int64_t)c * H * W;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        tvec<PX> o = tvec<PX>(0.f);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (i >= t.nterm) continue;
+#pragma unroll
+            for (int e = 0; e < PX; ++e) o[e] += seg_val(t.term[i], k[i], raw[dy][i][e], 0.f);
+        }
+#pragma unroll
+        for (int e = 0; e < PX; ++e) o[e] = apply_act(o[e], t.act, slope);
+        tail_st<PX>(out, (int64_t)(2 * qy + dy) * W + x0, o);
+    }
+}
+
+// The backward tails stay the two hand-written forms (tail_bwd_kernel: 2 x 2 units, int64
+// unit index, generic pointers; tail_bwd4_kernel: 2 x 4 units), with the helpers they call.
+// Folded into one template <int PX> body they kept every single-writer output bit for bit,
+// but the compiler paired and contracted the fp32 partial sums of term 0's centred statistic
+// (red[3]) differently, which moved that sum by a few fp32 ulps and, through it, every
+// training result (profiles/eltwise_fold.txt). A change to one form still has
+// to be repeated in the other.
 ISG_DEV float term_raw(const isg_vseg& t, int up, int n, int c, int H, int W, int y, int x,
                        float* yraw) {
     int64_t hw, pix;
@@ -64,59 +147,6 @@ ISG_DEV float term_raw(const isg_vseg& t, int up, int n, int c, int H, int W, in
     }
     *yraw = 0.f;
     return t.p[(int64_t)n * t.n_stride + (int64_t)c * hw + pix];
-}
-
-__global__ __launch_bounds__(kThreads) void tail_fwd_kernel(isg_tail t) {
-    const int c = blockIdx.y, n = blockIdx.z;
-    const int H = t.H, W = t.W;
-    const int qw = W >> 1;
-    const int64_t nq = (int64_t)(H >> 1) * qw;
-    const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (q >= nq) return;
-    const int qy = (int)(q / qw), qx = (int)(q - (int64_t)qy * qw);
-    const int64_t hw = (int64_t)H * W;
-    // the quad's raw term values first: their loads do not depend on the coefficients
-    // (consumer-side BatchNorm finalisation reads the statistics below), so both round
-    // trips overlap instead of running back to back
-    float2 raw[2][3];
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            raw[dy][i] = make_float2(0.f, 0.f);
-            if (i >= t.nterm) continue;
-            const isg_vseg& tm = t.term[i];
-            const int y = 2 * qy + dy;
-            if (t.up[i]) {
-                float dummy;
-                const float x0 = term_raw(tm, 1, n, c, H, W, y, 2 * qx, &dummy);
-                raw[dy][i] = make_float2(x0, x0);
-            } else {
-                const int64_t off = (int64_t)n * tm.n_stride + (int64_t)c * hw + (int64_t)y * W + 2 * qx;
-                raw[dy][i] = *reinterpret_cast<const float2*>(tm.p + off);
-            }
-        }
-    ChanCoef k[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        if (i < t.nterm) k[i] = seg_coef(t.term[i], c);
-    const float slope = (t.act == ISG_ACT_PRELU) ? t.slope[c] : 0.f;
-    float* out = t.out + (int64_t)n * t.out_n_stride + (int64_t)c * hw;
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy) {
-        float v[2] = {0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (i >= t.nterm) continue;
-            const isg_vseg& tm = t.term[i];
-            v[0] += seg_val(tm, k[i], raw[dy][i].x, 0.f);
-            v[1] += seg_val(tm, k[i], raw[dy][i].y, 0.f);
-        }
-        float2 o;
-        o.x = apply_act(v[0], t.act, slope);
-        o.y = apply_act(v[1], t.act, slope);
-        *reinterpret_cast<float2*>(out + (int64_t)(2 * qy + dy) * W + 2 * qx) = o;
-    }
 }
 
 __global__ __launch_bounds__(kThreads) void tail_bwd_kernel(isg_tail_grad tg) {
@@ -267,10 +297,6 @@ __global__ __launch_bounds__(kThreads) void tail_bwd_kernel(isg_tail_grad tg) {
     }
 }
 
-// ---- residual tail, 2 x 4 pixel units (W % 4 == 0, 16-B aligned planes) --------------
-// The same tails as above with a thread owning two rows of 4 pixels: every full-resolution
-// operand moves as 16-B accesses (an x2-upsampled term as one 8-B pair of low-resolution
-// values per row pair), half the threads, workgroups and reductions of the quad form.
 typedef f32x4 __attribute__((address_space(1)))* t4p;
 typedef const f32x4 __attribute__((address_space(1)))* tc4p;
 typedef float tf32x2 __attribute__((ext_vector_type(2)));
@@ -286,43 +312,6 @@ ISG_DEV f32x4 tail_term4(const isg_vseg& tm, int up, int n, int c, int H, int W,
     }
     const int64_t off = (int64_t)n * tm.n_stride + (int64_t)c * H * W + (int64_t)y * W + x4;
     return *(tc4p)((gcfloat_p)tm.p + off);
-}
-
-__global__ __launch_bounds__(kThreads) void tail_fwd4_kernel(isg_tail t) {
-    const int c = blockIdx.y, n = blockIdx.z;
-    const int H = t.H, W = t.W;
-    const int qw = W >> 2;
-    const int nq = (H >> 1) * qw;
-    const int q = blockIdx.x * kThreads + threadIdx.x;
-    if (q >= nq) return;
-    const int qy = q / qw, x4 = (q - qy * qw) * 4;
-    f32x4 raw[2][3];
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            raw[dy][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (i < t.nterm) raw[dy][i] = tail_term4(t.term[i], t.up[i], n, c, H, W, 2 * qy + dy, x4);
-        }
-    ChanCoef k[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        if (i < t.nterm) k[i] = seg_coef(t.term[i], c);
-    const float slope = (t.act == ISG_ACT_PRELU) ? t.slope[c] : 0.f;
-    float* out = t.out + (int64_t)n * t.out_n_stride + (int64_t)c * H * W;
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy) {
-        f32x4 o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            if (i >= t.nterm) continue;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] += seg_val(t.term[i], k[i], raw[dy][i][e], 0.f);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = apply_act(o[e], t.act, slope);
-        *(t4p)((gfloat_p)out + (int64_t)(2 * qy + dy) * W + x4) = o;
-    }
 }
 
 __global__ __launch_bounds__(kThreads) void tail_bwd4_kernel(isg_tail_grad tg) {
@@ -438,7 +427,7 @@ __global__ __launch_bounds__(kThreads) void tail_bwd4_kernel(isg_tail_grad tg) {
     }
 }
 
-// the 2 x 4 form applies: W % 4 == 0 and every full-resolution plane 16-B aligned (the
+// the PX = 4 form applies: W % 4 == 0 and every full-resolution plane 16-B aligned (the
 // upsampled terms 8-B), image strides multiples of 4 floats
 bool al(const void* p, int b) { return ((uintptr_t)p % b) == 0; }
 bool tail4_ok(const isg_tail& t, const isg_tail_grad* tg) {
@@ -455,6 +444,27 @@ bool tail4_ok(const isg_tail& t, const isg_tail_grad* tg) {
     if (!al(tg->dout, 16) || tg->dout_n_stride % 4) return false;
     if (tg->g && (!al(tg->g, 16) || tg->g_n_stride % 4)) return false;
     return true;
+}
+
+// what both directions refuse (dir: "fwd" / "bwd", for the message)
+int32_t tail_check(const isg_tail& t, const char* dir) {
+    if ((t.H & 1) || (t.W & 1) || t.nterm < 1 || t.nterm > 3)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "tail %s: H, W must be even, 1..3 terms", dir);
+    // the kernels count a plane's units, rounded up to whole workgroups, in int
+    if (((int64_t)t.H / 2) * (t.W / 2) > ((int64_t)1 << 31) - kThreads)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "tail %s: a plane of %d x %d pixels", dir, t.H, t.W);
+    for (int i = 0; i < t.nterm; ++i) {
+        if (isg_seg_res(t.term[i])) return isg_set_error(ISG_ERR_UNSUPPORTED, "tail %s: residual term form", dir);
+        // the tail kernels load no saved output y: a BN_BWD term would be rebuilt with y = 0
+        if (t.term[i].xform == ISG_XF_BN_BWD)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "tail %s: term %d is a BN_BWD segment", dir, i);
+    }
+    return ISG_OK;
+}
+
+// one thread per unit of two rows of px pixels, one (n, c) plane per grid.y, grid.z
+dim3 tail_grid(const isg_tail& t, int px) {
+    return dim3((unsigned)((((int64_t)t.H / 2) * (t.W / px) + kThreads - 1) / kThreads), t.C, t.N);
 }
 
 // ---- max-pool ---------------------------------------------------------------------
@@ -573,6 +583,21 @@ bool pool_vec_ok(const isg_vtensor& x, int k) {
     return true;
 }
 
+// what both directions refuse (res / res_msg: the caller's residual forms); sets *C to the
+// pooled tensor's channel count
+int32_t pool_check(const isg_vtensor* x, int k, bool res, const char* res_msg, int* C) {
+    if (k < 1 || x->H % k || x->W % k) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: H,W %% k");
+    if (res) return isg_set_error(ISG_ERR_UNSUPPORTED, "%s", res_msg);
+    *C = pool_channels(*x);
+    if (*C < 0) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: 1..%d segments, at most %d channels", ISG_MAX_SEGS, ISG_MAX_CH);
+    return ISG_OK;
+}
+
+// one thread per output pixel
+dim3 pool_grid(const isg_vtensor& x, int k, int C) {
+    return dim3((unsigned)(((int64_t)(x.H / k) * (x.W / k) + kThreads - 1) / kThreads), C, x.N);
+}
+
 // ---- BatchNorm running stats & gradient finalisation -------------------------------
 struct BnUpdateList {
     isg_bn_update it[ISG_LIST_CHUNK];
@@ -607,10 +632,7 @@ struct BnFinalList {
 
 // fwd: coef[c] = (mean, gamma*rstd, beta, 0); bwd: coef[C + c] = (A, B, mean, Cc) — the
 // exact values fwd_coef / bwd_coef (common.h) compute from the statistics.
-__global__ void bn_finalize_kernel(BnFinalList items, int nitems, int bwd) {
-    const int it = blockIdx.x;
-    if (it >= nitems) return;
-    isg_bn bn = items.it[it];
+ISG_DEV void bn_finalize_item(isg_bn bn, int bwd) {
     float* out = bn.coef;
     bn.coef = nullptr;  // evaluate from the statistics
     for (int c = threadIdx.x; c < bn.C; c += blockDim.x) {
@@ -624,21 +646,15 @@ __global__ void bn_finalize_kernel(BnFinalList items, int nitems, int bwd) {
     }
 }
 
+__global__ void bn_finalize_kernel(BnFinalList items, int nitems, int bwd) {
+    const int it = blockIdx.x;
+    if (it >= nitems) return;
+    bn_finalize_item(items.it[it], bwd);
+}
+
 // one layer (the executor's per-BN-point launches): a 64-B kernel argument instead of the
 // ISG_LIST_CHUNK-item list
-__global__ void bn_finalize1_kernel(isg_bn bn, int bwd) {
-    float* out = bn.coef;
-    bn.coef = nullptr;
-    for (int c = threadIdx.x; c < bn.C; c += blockDim.x) {
-        if (!bwd) {
-            const ChanCoef k = fwd_coef(bn, nullptr, c);
-            reinterpret_cast<f32x4*>(out)[c] = f32x4{k.c0, k.c1, k.c2, 0.f};
-        } else {
-            const ChanCoef k = bwd_coef(bn, c);
-            reinterpret_cast<f32x4*>(out)[bn.C + c] = f32x4{k.c0, k.c1, k.c2, k.c3};
-        }
-    }
-}
+__global__ void bn_finalize1_kernel(isg_bn bn, int bwd) { bn_finalize_item(bn, bwd); }
 
 // one item's values; put(dst, value) stores each (grad_final_kernel: a plain store; the
 // fused step tail: the store plus that element's Adam update)
@@ -693,9 +709,8 @@ __global__ void grad_final_kernel(GradFinalList items, int nitems) {
 }
 
 // ---- sigmoid + BCE ----------------------------------------------------------------
-// the per-element arithmetic of bce_kernel below, one 16-B quad per thread: both loads in
-// flight at once and one pass (the strided loop waited out one load round trip per
-// element group: 21 us for the 2 x 1024^2 logits of the bench step)
+// One element, with contraction off (torch's clamps): returns the loss and forms the
+// gradient g. Both kernels below call it, so their dlogits agree bit for bit.
 ISG_DEV float bce_elem(float x, float t, float grad_scale, float& g) {
 #pragma clang fp contract(off)
     const float p = 1.f / (1.f + expf(-x));
@@ -703,6 +718,8 @@ ISG_DEV float bce_elem(float x, float t, float grad_scale, float& g) {
     float l1p = logf(1.f - p);
     lp = lp < -100.f ? -100.f : lp;
     l1p = l1p < -100.f ? -100.f : l1p;
+    // torch binary_cross_entropy_backward: grad*(p-t)/max((1-p)*p, 1e-12),
+    // then sigmoid_backward: g*(1-p)*p
     float den = (1.f - p) * p;
     den = den < 1e-12f ? 1e-12f : den;
     const float gp = grad_scale * (p - t) / den;
@@ -710,7 +727,9 @@ ISG_DEV float bce_elem(float x, float t, float grad_scale, float& g) {
     return -(t * lp + (1.f - t) * l1p);
 }
 
-// kBceQ quads per thread (all loads in flight): the loss sum is one fp64 atomic per
+// 16-B quads, both operands' loads in flight at once and one pass (bce_kernel's strided
+// loop waits out one load round trip per element group: 21 us for the 2 x 1024^2 logits of
+// the bench step). kBceQ quads per thread (all loads in flight): the loss sum is one fp64 atomic per
 // workgroup on ONE address, which serialises — with a quad per thread (2048 workgroups at
 // the bench size) those atomics alone took ~30 us
 constexpr int kBceQ = 8;
@@ -751,28 +770,13 @@ __global__ __launch_bounds__(kThreads) void bce4_kernel(const float* logits, con
 __global__ __launch_bounds__(kThreads) void bce_kernel(const float* logits, const float* target,
                                                         int64_t n, double* loss_acc, float* dlogits,
                                                         float grad_scale) {
-#pragma clang fp contract(off)
     __shared__ double sh[4];
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * kThreads) {
-        const float x = logits[i];
-        const float t = target[i];
-        const float p = 1.f / (1.f + expf(-x));
-        float lp = logf(p);
-        float l1p = logf(1.f - p);
-        lp = lp < -100.f ? -100.f : lp;
-        l1p = l1p < -100.f ? -100.f : l1p;
-        const float l = -(t * lp + (1.f - t) * l1p);
-        acc += (double)l;
-        if (dlogits) {
-            // torch binary_cross_entropy_backward: grad*(p-t)/max((1-p)*p, 1e-12),
-            // then sigmoid_backward: g*(1-p)*p
-            float den = (1.f - p) * p;
-            den = den < 1e-12f ? 1e-12f : den;
-            const float gp = grad_scale * (p - t) / den;
-            dlogits[i] = gp * (1.f - p) * p;
-        }
+        float g;
+        acc += (double)bce_elem(logits[i], target[i], grad_scale, g);
+        if (dlogits) dlogits[i] = g;
     }
     acc = wave_sum_d(acc);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -798,28 +802,9 @@ __global__ void sigmoid_bwd_kernel(const float* y, const float* dy, float* dx, i
 // torch.optim.Adam single-tensor math (torch 2.10 _single_tensor_adam):
 //   m.lerp_(g, 1-b1); v = v*b2 + (1-b2)*g*g; denom = sqrt(v)/sqrt(bc2) + eps;
 //   p += (-lr/bc1) * m / denom
-__global__ void adam_kernel(float* p, const float* g, float* m, float* v, const uint8_t* live,
-                            int64_t n, float w1, float b2, float one_m_b2, float bc2_sqrt,
-                            float neg_step, float eps, float wd) {
-#pragma clang fp contract(off)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        if (live && !live[i]) continue;
-        float gi = g[i];
-        const float pi = p[i];
-        if (wd != 0.f) gi = gi + wd * pi;
-        float mi = m[i];
-        mi = mi + w1 * (gi - mi);  // lerp with weight < 0.5
-        float vi = v[i] * b2;
-        vi = vi + one_m_b2 * gi * gi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = pi + neg_step * mi / denom;
-    }
-}
-
-// Graph-replayable form: the 1-based step lives in device memory (incremented by
+// One element's update (adam_elem) serves three kernels: adam_kernel takes the coefficients
+// from the host, adam_dev_kernel and the fused step tail form them on the device.
+// The graph-replayable form: the 1-based step lives in device memory (incremented by
 // step_inc_kernel earlier in the same stream), bias corrections are formed in double
 // exactly like torch's host-side python floats, then rounded to f32. The hyperparameters
 // arrive as doubles (torch's python floats): torch rounds 1-beta1 and 1-beta2 from the
@@ -850,13 +835,22 @@ ISG_DEV void adam_elem(float* p, float* m, float* v, int64_t i, float gi, const 
     const float pi = p[i];
     if (k.wdf != 0.f) gi = gi + k.wdf * pi;
     float mi = m[i];
-    mi = mi + k.w1 * (gi - mi);
+    mi = mi + k.w1 * (gi - mi);  // lerp with weight < 0.5
     float vi = v[i] * k.b2f;
     vi = vi + k.one_m_b2 * gi * gi;
     const float denom = sqrtf(vi) / k.bc2_sqrt + k.epsf;
     m[i] = mi;
     v[i] = vi;
     p[i] = pi + k.neg_step * mi / denom;
+}
+
+__global__ void adam_kernel(float* p, const float* g, float* m, float* v, const uint8_t* live,
+                            int64_t n, AdamCoef k) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (live && !live[i]) continue;
+        adam_elem(p, m, v, i, g[i], k);
+    }
 }
 
 __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, const uint8_t* live,
@@ -870,11 +864,26 @@ __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, co
     }
 }
 
+// Element i of NREP weight-gradient replicas folded to fp32, NREP known at compile time:
+// every replica's load is issued before the first add (the runtime-count loop waited one
+// round trip per replica: 23 us for the 16 x 266k fp64 replicas of the bench step); summed
+// in replica order
+template <int NREP>
+ISG_DEV float fold_rep(const double* src, int64_t stride, int64_t i) {
+    double v[NREP];
+#pragma unroll
+    for (int r = 0; r < NREP; ++r) v[r] = gld_d(src, r * stride + i);
+    double a = v[0];
+#pragma unroll
+    for (int r = 1; r < NREP; ++r) a += v[r];
+    return (float)a;
+}
+
 // The end of a world-1 training step in ONE launch (isg.h isg_step_tail): workgroups
 // [0, nfold) fold the weight-gradient replicas into the flat gradient and apply Adam to each
 // folded element; the next ngf fold the statistics-derived gradients (grad_final_item) and
 // apply Adam to those; the last nbnu update the BatchNorm running statistics. Element
-// arithmetic is sum_rep_n_kernel's, grad_final_kernel's and adam_dev_kernel's (the same
+// arithmetic is sum_rep_n_kernel's (fold_rep), grad_final_kernel's and adam_dev_kernel's (the same
 // device functions), so the result is bitwise that of the separate launches, which ran as
 // 1 + 5 + 1 (+1 step counter) launches hopping between streams, plus 3 BN-update launches
 // on the forward's critical path.
@@ -896,13 +905,7 @@ __global__ __launch_bounds__(kThreads) void step_tail_kernel(isg_step_tail_args 
         if (i >= a.n) return;
         const uint8_t o = a.owner[i];
         if (o & 2) return;  // written by a grad_final item below
-        double v[NREP];
-#pragma unroll
-        for (int r = 0; r < NREP; ++r) v[r] = gld_d(a.rep, r * a.n + i);
-        double s = v[0];
-#pragma unroll
-        for (int r = 1; r < NREP; ++r) s += v[r];
-        const float g = (float)s;
+        const float g = fold_rep<NREP>(a.rep, a.n, i);
         a.grad[i] = g;
         if (o & 1) adam_elem(a.param, a.exp_avg, a.exp_avg_sq, i, g, k);
         return;
@@ -939,23 +942,15 @@ __global__ void fill_f64_kernel(double* p, int64_t n, double v) {
 }
 
 // Fold the ISG_WREP weight-gradient replicas: dst[i] = sum_r src[r*stride + i] (fixed
-// order), 4 elements per lane with 16-B loads where the layout allows.
-// NREP replicas known at compile time: every replica's load of the thread's 2 elements is
-// issued before the first add (the runtime-count loop waited one round trip per replica:
-// 23 us for the 16 x 266k fp64 replicas of the bench step); summed in replica order
+// order): one element per thread for a compile-time count (fold_rep), else 4 elements per
+// lane with 16-B loads where the layout allows.
 template <int NREP>
 __global__ __launch_bounds__(kThreads) void sum_rep_n_kernel(float* __restrict__ dst,
                                                              const double* __restrict__ src, int64_t n,
                                                              int64_t stride) {
     const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
-    double v[NREP];
-#pragma unroll
-    for (int r = 0; r < NREP; ++r) v[r] = gld_d(src, r * stride + i);
-    double a = v[0];
-#pragma unroll
-    for (int r = 1; r < NREP; ++r) a += v[r];
-    gst(dst, i, (float)a);
+    gst(dst, i, fold_rep<NREP>(src, stride, i));
 }
 
 __global__ __launch_bounds__(kThreads) void sum_rep_kernel(float* __restrict__ dst,
@@ -989,42 +984,39 @@ unsigned grid_for(int64_t n, int cap = 2048) {
     return (unsigned)b;
 }
 
+// f(std::integral_constant<int, nrep>) for the replica counts built as compile-time
+// folds (fold_rep); false, and no call, for any other count
+template <class F>
+bool with_nrep(int nrep, F f) {
+    if (nrep == 16) f(std::integral_constant<int, 16>());
+    else if (nrep == 8) f(std::integral_constant<int, 8>());
+    else if (nrep == 4) f(std::integral_constant<int, 4>());
+    else return false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
 
 int32_t isg_tail_fwd(const isg_tail* t, isg_stream_t st) {
-    if ((t->H & 1) || (t->W & 1) || t->nterm < 1 || t->nterm > 3)
-        return isg_set_error(ISG_ERR_UNSUPPORTED, "tail fwd: H, W must be even, 1..3 terms");
-    for (int i = 0; i < t->nterm; ++i) {
-        if (isg_seg_res(t->term[i])) return isg_set_error(ISG_ERR_UNSUPPORTED, "tail fwd: residual term form");
-        // the tail kernels load no saved output y: a BN_BWD term would be rebuilt with y = 0
-        if (t->term[i].xform == ISG_XF_BN_BWD)
-            return isg_set_error(ISG_ERR_UNSUPPORTED, "tail fwd: term %d is a BN_BWD segment", i);
-    }
+    if (int32_t e = tail_check(*t, "fwd")) return e;
     if (tail4_ok(*t, nullptr)) {
-        dim3 grid4((unsigned)((((int64_t)t->H / 2) * (t->W / 4) + kThreads - 1) / kThreads), t->C, t->N);
-        hipLaunchKernelGGL(tail_fwd4_kernel, grid4, dim3(kThreads), 0, st, *t);
-        return isg_check_launch("tail_fwd4_kernel");
+        hipLaunchKernelGGL(tail_fwd_kernel<4>, tail_grid(*t, 4), dim3(kThreads), 0, st, *t);
+        return isg_check_launch("tail_fwd_kernel<4>");
     }
-    dim3 grid((unsigned)((((int64_t)t->H / 2) * (t->W / 2) + kThreads - 1) / kThreads), t->C, t->N);
-    hipLaunchKernelGGL(tail_fwd_kernel, grid, dim3(kThreads), 0, st, *t);
-    return isg_check_launch("tail_fwd_kernel");
+    hipLaunchKernelGGL(tail_fwd_kernel<2>, tail_grid(*t, 2), dim3(kThreads), 0, st, *t);
+    return isg_check_launch("tail_fwd_kernel<2>");
 }
 
 int32_t isg_tail_bwd(const isg_tail_grad* t, isg_stream_t st) {
     const isg_tail& f = t->f;
-    if ((f.H & 1) || (f.W & 1) || f.nterm < 1 || f.nterm > 3)
-        return isg_set_error(ISG_ERR_UNSUPPORTED, "tail bwd: H, W must be even, 1..3 terms");
-    for (int i = 0; i < f.nterm; ++i) {
-        if (isg_seg_res(f.term[i])) return isg_set_error(ISG_ERR_UNSUPPORTED, "tail bwd: residual term form");
-        if (f.term[i].xform == ISG_XF_BN_BWD)
-            return isg_set_error(ISG_ERR_UNSUPPORTED, "tail bwd: term %d is a BN_BWD segment", i);
-        // g is the gradient of the SUM: the kernels do not differentiate a term's own
-        // activation (the forward applies it)
+    if (int32_t e = tail_check(f, "bwd")) return e;
+    // g is the gradient of the SUM: the kernels do not differentiate a term's own
+    // activation (the forward applies it)
+    for (int i = 0; i < f.nterm; ++i)
         if (f.term[i].xform == ISG_XF_BN_FWD && f.term[i].act != ISG_ACT_NONE)
             return isg_set_error(ISG_ERR_UNSUPPORTED, "tail bwd: term %d has an activation of its own", i);
-    }
     // the kernels load every accumulating term's old value before any write:
     // two terms accumulating into one destination would lose one contribution
     for (int i = 0; i < f.nterm; ++i)
@@ -1032,35 +1024,28 @@ int32_t isg_tail_bwd(const isg_tail_grad* t, isg_stream_t st) {
             if (t->dterm[i] && t->dterm[i] == t->dterm[j] && (t->dterm_accum[i] || t->dterm_accum[j]))
                 return isg_set_error(ISG_ERR_INVALID, "tail bwd: terms %d and %d share a gradient destination", i, j);
     if (tail4_ok(f, t)) {
-        dim3 grid4((unsigned)((((int64_t)f.H / 2) * (f.W / 4) + kThreads - 1) / kThreads), f.C, f.N);
-        hipLaunchKernelGGL(tail_bwd4_kernel, grid4, dim3(kThreads), 0, st, *t);
+        hipLaunchKernelGGL(tail_bwd4_kernel, tail_grid(f, 4), dim3(kThreads), 0, st, *t);
         return isg_check_launch("tail_bwd4_kernel");
     }
-    dim3 grid((unsigned)((((int64_t)f.H / 2) * (f.W / 2) + kThreads - 1) / kThreads), f.C, f.N);
-    hipLaunchKernelGGL(tail_bwd_kernel, grid, dim3(kThreads), 0, st, *t);
+    hipLaunchKernelGGL(tail_bwd_kernel, tail_grid(f, 2), dim3(kThreads), 0, st, *t);
     return isg_check_launch("tail_bwd_kernel");
 }
 
 int32_t isg_maxpool_fwd(const isg_vtensor* x, int32_t k, float* out, int64_t out_n_stride,
                         isg_stream_t st) {
-    if (k < 1 || x->H % k || x->W % k) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: H,W %% k");
-    if (isg_vt_res(x)) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: residual input form");
-    const int C = pool_channels(*x);
-    if (C < 0) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: 1..%d segments, at most %d channels", ISG_MAX_SEGS, ISG_MAX_CH);
+    int C;
+    if (int32_t e = pool_check(x, k, isg_vt_res(x), "maxpool: residual input form", &C)) return e;
     PoolArgs a{};
     a.x = *x; a.k = k; a.out = out; a.out_n_stride = out_n_stride;
     a.vec = pool_vec_ok(*x, k) ? 1 : 0;
-    dim3 grid((unsigned)(((int64_t)(x->H / k) * (x->W / k) + kThreads - 1) / kThreads), C, x->N);
-    hipLaunchKernelGGL(maxpool_kernel<false>, grid, dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL(maxpool_kernel<false>, pool_grid(*x, k, C),dim3(kThreads), 0, st, a);
     return isg_check_launch("maxpool_kernel<fwd>");
 }
 
 int32_t isg_maxpool_bwd(const isg_vtensor* x, int32_t k, const float* dout, int64_t dout_n_stride,
                         const isg_sinks* dx, isg_stream_t st) {
-    if (k < 1 || x->H % k || x->W % k) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: H,W %% k");
-    if (isg_vt_res(x) || isg_sinks_res(dx)) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: residual form");
-    const int C = pool_channels(*x);
-    if (C < 0) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool: 1..%d segments, at most %d channels", ISG_MAX_SEGS, ISG_MAX_CH);
+    int C;
+    if (int32_t e = pool_check(x, k, isg_vt_res(x) || isg_sinks_res(dx), "maxpool: residual form", &C)) return e;
     // sink_of picks a sink by its c0 alone: the sinks must tile [0, C) in order
     if (dx->nsink < 1 || dx->nsink > ISG_MAX_SEGS)
         return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool bwd: 1..%d sinks", ISG_MAX_SEGS);
@@ -1075,8 +1060,7 @@ int32_t isg_maxpool_bwd(const isg_vtensor* x, int32_t k, const float* dout, int6
     if (cs != C) return isg_set_error(ISG_ERR_UNSUPPORTED, "maxpool bwd: the sinks do not cover channels [0, %d)", C);
     PoolArgs a{};
     a.x = *x; a.k = k; a.dout = dout; a.dout_n_stride = dout_n_stride; a.dx = *dx;
-    dim3 grid((unsigned)(((int64_t)(x->H / k) * (x->W / k) + kThreads - 1) / kThreads), C, x->N);
-    hipLaunchKernelGGL(maxpool_kernel<true>, grid, dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL(maxpool_kernel<true>, pool_grid(*x, k, C), dim3(kThreads), 0, st, a);
     return isg_check_launch("maxpool_kernel<bwd>");
 }
 
@@ -1153,11 +1137,16 @@ int32_t isg_adam(float* param, const float* grad, float* exp_avg, float* exp_avg
     // scalar math in double exactly like torch's python-side bias corrections
     const double bc1 = 1.0 - std::pow(beta1, (double)step);
     const double bc2 = 1.0 - std::pow(beta2, (double)step);
-    const float neg_step = (float)(-(lr / bc1));
-    const float bc2_sqrt = (float)std::sqrt(bc2);
+    AdamCoef k;
+    k.neg_step = (float)(-(lr / bc1));
+    k.bc2_sqrt = (float)std::sqrt(bc2);
+    k.w1 = (float)(1.0 - beta1);
+    k.b2f = (float)beta2;
+    k.one_m_b2 = (float)(1.0 - beta2);
+    k.epsf = (float)eps;
+    k.wdf = (float)weight_decay;
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(kThreads), 0, st, param, grad, exp_avg,
-                       exp_avg_sq, live, n, (float)(1.0 - beta1), (float)beta2,
-                       (float)(1.0 - beta2), bc2_sqrt, neg_step, (float)eps, (float)weight_decay);
+                       exp_avg_sq, live, n, k);
     return isg_check_launch("adam_kernel");
 }
 
@@ -1181,9 +1170,9 @@ int32_t isg_step_tail(const isg_step_tail_args* a, isg_stream_t st) {
     const int64_t grid = nfold + a->ngf + a->nbnu;
     if (grid < 1) return ISG_OK;
     if (grid >= ((int64_t)1 << 31)) return isg_set_error(ISG_ERR_UNSUPPORTED, "step tail: %lld elements", (long long)a->n);
-    if (a->nrep == 16) hipLaunchKernelGGL(step_tail_kernel<16>, dim3((unsigned)grid), dim3(kThreads), 0, st, *a, (int)nfold);
-    else if (a->nrep == 8) hipLaunchKernelGGL(step_tail_kernel<8>, dim3((unsigned)grid), dim3(kThreads), 0, st, *a, (int)nfold);
-    else hipLaunchKernelGGL(step_tail_kernel<4>, dim3((unsigned)grid), dim3(kThreads), 0, st, *a, (int)nfold);
+    with_nrep(a->nrep, [&](auto R) {
+        hipLaunchKernelGGL(step_tail_kernel<decltype(R)::value>, dim3((unsigned)grid), dim3(kThreads), 0, st, *a, (int)nfold);
+    });
     return isg_check_launch("step_tail_kernel");
 }
 
@@ -1198,13 +1187,11 @@ int32_t isg_sum_replicas(float* dst, const double* src, int64_t n, int32_t nrep,
     if (n <= 0) return 0;
     if (!dst || !src || nrep < 1 || (nrep > 1 && stride < n))
         return isg_set_error(ISG_ERR_INVALID, "sum_replicas: bad arguments");
-    if (nrep == 16 || nrep == 8 || nrep == 4) {
-        const int64_t b1 = (n + kThreads - 1) / kThreads;
-        if (nrep == 16) hipLaunchKernelGGL(sum_rep_n_kernel<16>, dim3((unsigned)b1), dim3(kThreads), 0, st, dst, src, n, stride);
-        else if (nrep == 8) hipLaunchKernelGGL(sum_rep_n_kernel<8>, dim3((unsigned)b1), dim3(kThreads), 0, st, dst, src, n, stride);
-        else hipLaunchKernelGGL(sum_rep_n_kernel<4>, dim3((unsigned)b1), dim3(kThreads), 0, st, dst, src, n, stride);
+    const int64_t b1 = (n + kThreads - 1) / kThreads;
+    if (with_nrep(nrep, [&](auto R) {
+            hipLaunchKernelGGL(sum_rep_n_kernel<decltype(R)::value>, dim3((unsigned)b1), dim3(kThreads), 0, st, dst, src, n, stride);
+        }))
         return isg_check_launch("sum_rep_n_kernel");
-    }
     const int64_t blocks = ((n + 3) / 4 + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(sum_rep_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, dst, src, n,
                        nrep, stride);

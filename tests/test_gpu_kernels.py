@@ -799,7 +799,7 @@ def test_maxpool(k):
 @pytest.mark.parametrize("H,W,accum", [(128, 132, True), (16, 14, False)],
                          ids=["128x132_2x4_accum", "16x14_quad"])
 def test_tail(act, up, H, W, accum):
-    """A >= 128^2 plane with W % 4 == 0 runs the 2x4-unit kernels (tail_fwd4 / tail_bwd4),
+    """A >= 128^2 plane with W % 4 == 0 runs the 2x4-unit kernels (tail_fwd<4> / tail_bwd4),
     16 x 14 the 2x2 form; accum: the term gradient adds onto an existing value (prefetched
     old value)."""
     N, C = 2, 8
