@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "../../include/isg.h"
-#include "residual.h"
+#include "launch.h"
 
 static thread_local std::string g_last_error;
 
@@ -30,20 +30,6 @@ int32_t isg_check_launch(const char* what) {
     if (e != hipSuccess) return isg_set_error(ISG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     return ISG_OK;
 }
-
-// implemented in conv_mfma.hip / dw_convt.hip
-int32_t isg_dense_conv_fwd(const isg_conv_geom*, const isg_vtensor*, const float*, const isg_sinks*,
-                           hipStream_t);
-int32_t isg_dense_conv_dgrad(const isg_conv_geom*, const isg_vtensor*, const float*, const isg_sinks*,
-                             hipStream_t);
-int32_t isg_dense_conv_wgrad(const isg_conv_geom*, const isg_vtensor*, const isg_vtensor*, double*,
-                             double*, int64_t, int32_t, hipStream_t);
-int32_t isg_depthwise_fwd(const isg_conv_geom*, const isg_vtensor*, const float*, const isg_sinks*,
-                          hipStream_t);
-int32_t isg_depthwise_dgrad(const isg_conv_geom*, const isg_vtensor*, const float*, const isg_sinks*,
-                            hipStream_t);
-int32_t isg_depthwise_wgrad(const isg_conv_geom*, const isg_vtensor*, const isg_vtensor*, double*,
-                            double*, int64_t, int32_t, hipStream_t);
 
 static int32_t check_geom(const isg_conv_geom* g) {
     if (!g) return isg_set_error(ISG_ERR_INVALID, "conv: NULL geometry");
@@ -66,15 +52,9 @@ static int32_t check_geom(const isg_conv_geom* g) {
 
 static bool geom_ok(const isg_conv_geom* g) { return check_geom(g) == ISG_OK; }
 
-int32_t isg_tap_conv(const isg_conv_geom*, const isg_vtensor*, const float*, const isg_sinks*,
-                     bool, hipStream_t);
-int32_t isg_pw_gemm(const isg_conv_geom*, const isg_vtensor*, const float*, const isg_sinks*, bool,
-                    hipStream_t);
-
 // the residual forms (isg.h) exist for the 1x1 stride-1 dense conv only
 static bool pointwise(const isg_conv_geom* g) {
-    return g->KH == 1 && g->KW == 1 && g->SH == 1 && g->SW == 1 && g->PH == 0 && g->PW == 0 &&
-           g->DH == 1 && g->DW == 1 && g->groups == 1 && g->w_ci == 0;
+    return geom_1x1_s1(g) && g->DH == 1 && g->DW == 1 && g->groups == 1 && g->w_ci == 0;
 }
 // segments covering `cin` channels in (forward: one), consecutive sinks covering all `cout`
 // rows out (input gradient: one)
@@ -91,18 +71,10 @@ static bool res_shape_ok(const isg_vtensor* v, int cin, const isg_sinks* k, int 
     }
     return c == cout;
 }
-int32_t isg_s2k5_fwd(const isg_conv_geom*, const isg_vtensor*, const float*, const isg_sinks*,
-                     hipStream_t);
-int32_t isg_s2k5_wgrad(const isg_conv_geom*, const isg_vtensor*, const isg_vtensor*, double*, double*,
-                       int64_t, int32_t, hipStream_t);
-int32_t isg_tap_wgrad(const isg_conv_geom*, const isg_vtensor*, const isg_vtensor*, double*, double*,
-                      int64_t, int32_t, hipStream_t);
 
 // a conv over the first Ci of the weight's w_ci input channels (the keypoint stem's RGB
 // part): only tap_conv / tap_wgrad index the weight with a separate channel count
 static bool partial_w(const isg_conv_geom* g) { return g->w_ci > 0 && g->w_ci != g->Ci; }
-
-static isg_vtensor resolve_y(const isg_vtensor* v) { return isg_resolve_y(v); }  // residual.h
 
 extern "C" {
 
@@ -120,15 +92,13 @@ int32_t isg_conv_fwd(const isg_conv_geom* g, const isg_vtensor* x_, const float*
             return isg_set_error(ISG_ERR_UNSUPPORTED, "conv fwd: residual input needs a 1x1 conv and one segment");
         return isg_pw_gemm(g, x_, w, out, false, st);
     }
-    const isg_vtensor xr = resolve_y(x_);
+    const isg_vtensor xr = isg_resolve_y(x_);
     const isg_vtensor* x = &xr;
     if (partial_w(g)) {
         // the stem's RGB layer 1 (5x5 s2, weight over w_ci = 20 channels): s2k5_fwd_kernel
-        const int32_t s = isg_s2k5_fwd(g, x, w, out, st);
-        if (s != 0) return s < 0 ? s : ISG_OK;
-        const int32_t t = isg_tap_conv(g, x, w, out, false, st);
-        if (t < 0) return t;
-        return t ? ISG_OK : isg_set_error(ISG_ERR_UNSUPPORTED, "conv fwd: w_ci %d != Ci %d off tap_conv", g->w_ci, g->Ci);
+        ISG_TRY(isg_s2k5_fwd(g, x, w, out, st));
+        ISG_TRY(isg_tap_conv(g, x, w, out, false, st));
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "conv fwd: w_ci %d != Ci %d off tap_conv", g->w_ci, g->Ci);
     }
     if (g->groups == 1) return isg_dense_conv_fwd(g, x, w, out, st);
     return isg_depthwise_fwd(g, x, w, out, st);
@@ -139,7 +109,7 @@ int32_t isg_conv_dgrad(const isg_conv_geom* g, const isg_vtensor* dy_, const flo
     if (int32_t e = check_geom(g)) return e;
     if (!dy_ || !dx) return isg_set_error(ISG_ERR_INVALID, "conv dgrad: NULL tensor");
     if (isg_vt_res(dy_)) return isg_set_error(ISG_ERR_UNSUPPORTED, "conv dgrad: residual input form");
-    const isg_vtensor dyr = resolve_y(dy_);
+    const isg_vtensor dyr = isg_resolve_y(dy_);
     const isg_vtensor* dy = &dyr;
     if (isg_sinks_res(dx)) {  // a folded residual tail's backward: the slab 1x1 GEMM or nothing
         if (!pointwise(g) || !res_shape_ok(dy, g->Co, dx, g->Ci, true))
@@ -157,7 +127,7 @@ int32_t isg_conv_wgrad_rep(const isg_conv_geom* g, const isg_vtensor* dy_, const
     if (int32_t e = check_geom(g)) return e;
     if (isg_vt_res(dy_) || isg_vt_res(x_))
         return isg_set_error(ISG_ERR_UNSUPPORTED, "conv wgrad: residual input form");
-    const isg_vtensor dyr = resolve_y(dy_), xr = resolve_y(x_);
+    const isg_vtensor dyr = isg_resolve_y(dy_), xr = isg_resolve_y(x_);
     const isg_vtensor *dy = &dyr, *x = &xr;
     if (nrep < 1 || (nrep > 1 && rep_stride <= 0))
         return isg_set_error(ISG_ERR_INVALID, "conv wgrad: bad replicas %d / stride %lld", nrep,
@@ -165,11 +135,9 @@ int32_t isg_conv_wgrad_rep(const isg_conv_geom* g, const isg_vtensor* dy_, const
     if (!dy_ || !x_) return isg_set_error(ISG_ERR_INVALID, "conv wgrad: NULL tensor");
     if (partial_w(g)) {
         // the stem's RGB layer 1 (weight over w_ci = 20 channels): s2k5_wgrad_kernel
-        const int32_t s = isg_s2k5_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st);
-        if (s != 0) return s < 0 ? s : ISG_OK;
-        const int32_t t = isg_tap_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st);
-        if (t < 0) return t;
-        return t ? ISG_OK : isg_set_error(ISG_ERR_UNSUPPORTED, "conv wgrad: w_ci %d != Ci %d off tap_wgrad", g->w_ci, g->Ci);
+        ISG_TRY(isg_s2k5_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st));
+        ISG_TRY(isg_tap_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st));
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "conv wgrad: w_ci %d != Ci %d off tap_wgrad", g->w_ci, g->Ci);
     }
     if (g->groups == 1) return isg_dense_conv_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st);
     return isg_depthwise_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st);
@@ -317,13 +285,6 @@ struct Fix {
     int32_t loc, slot;
     int64_t offset;
 };
-
-// wgrad.hip: grouped 1x1 weight gradients (the executor's side-stream batches)
-int32_t isg_pwg_plan_bytes();
-int32_t isg_pwg_group_max();
-int32_t isg_pwg_plan(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x, double* dw,
-                     double* dbias, int64_t rep_stride, int32_t nrep, void* plan);
-int32_t isg_pwg_run(const void* const* plans, int32_t n, hipStream_t st);
 
 static int32_t run_op(int32_t kind, char* buf, isg_stream_t st) {
     int32_t rc = 0;

@@ -11,10 +11,11 @@
 #include <stdint.h>
 
 #include "../../include/isg.h"
-#include "residual.h"
+#include "launch.h"
 
 #define ISG_DEV __device__ __forceinline__
 #define ISG_DEV_HOST __host__ __device__ inline
+#define ISG_HD __host__ __device__ __forceinline__  // ISG_DEV, callable from the host too
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -378,7 +379,3 @@ static __device__ unsigned long long isg_stamps[ISG_STAMP_MAXBLK * 8];
 #define STAMP(i) do {} while (0)
 #define ISG_STAMP_ACCESSOR(name)
 #endif
-
-// ---- error plumbing (host) -----------------------------------------------------
-int32_t isg_set_error(int32_t code, const char* fmt, ...);
-int32_t isg_check_launch(const char* what);

@@ -201,12 +201,6 @@ __global__ __launch_bounds__(kThreads) void gemm_conv_kernel(GemmArgs a) {
     }
 }
 
-int vt_channels(const isg_vtensor* v) {
-    int c = 0;
-    for (int i = 0; i < v->nseg; ++i) c += v->s[i].C;
-    return c;
-}
-
 int num_blocks_for(int64_t ntiles) {
     int64_t b = (ntiles + kWaves - 1) / kWaves;
     if (b > 4096) b = 4096;
@@ -249,56 +243,25 @@ int32_t check_sinks(const isg_sinks* s, int M, const char* what) {
 
 }  // namespace
 
-int32_t isg_halo_conv_fwd(const isg_conv_geom* g, const isg_vtensor* x, const float* w,
-                          const isg_sinks* out, hipStream_t st);
-int32_t isg_pw_gemm(const isg_conv_geom* g, const isg_vtensor* src, const float* w,
-                    const isg_sinks* out, bool dgrad, hipStream_t st);
-int32_t isg_tap_conv(const isg_conv_geom* g, const isg_vtensor* src, const float* w,
-                     const isg_sinks* out, bool dgrad, hipStream_t st);
-int32_t isg_thin_conv(const isg_conv_geom* g, const isg_vtensor* src, const float* w,
-                      const isg_sinks* out, bool dgrad, hipStream_t st);
-
+// the 1x1 stride-1 GEMM's shapes (pw_gemm.hip)
 static bool is_pointwise(const isg_conv_geom* g) {
-    return g->KH == 1 && g->KW == 1 && g->SH == 1 && g->SW == 1 && g->PH == 0 && g->PW == 0 &&
-           g->groups == 1 && g->Ci <= 256 && g->Co <= 256;
+    return geom_1x1_s1(g) && g->groups == 1 && g->Ci <= 256 && g->Co <= 256;
 }
-
-int32_t isg_down_conv_fwd(const isg_conv_geom* g, const isg_vtensor* src, const float* w,
-                          const isg_sinks* out, hipStream_t st);
-int32_t isg_s2k5_fwd(const isg_conv_geom* g, const isg_vtensor* x, const float* w,
-                     const isg_sinks* out, hipStream_t st);
-int32_t isg_sub2_dgrad(const isg_conv_geom* g, const isg_vtensor* dy, const float* w,
-                       const isg_sinks* dx, hipStream_t st);
 
 int32_t isg_dense_conv_fwd(const isg_conv_geom* g, const isg_vtensor* x, const float* w,
                            const isg_sinks* out, hipStream_t st) {
     if (vt_channels(x) != g->Ci) return isg_set_error(ISG_ERR_INVALID, "conv fwd: Ci mismatch");
     if (int32_t e = check_sinks(out, g->Co, "conv fwd")) return e;
     if (is_pointwise(g)) return isg_pw_gemm(g, x, w, out, false, st);
-    {  // thin stride-1 convs on the VALU (thin_conv.hip)
-        const int32_t t = isg_thin_conv(g, x, w, out, false, st);
-        if (t != 0) return t < 0 ? t : 0;
-    }
-    {  // k 2S, stride S: the sub-pixel convT's input gradient (down_conv.hip)
-        const int32_t t = isg_down_conv_fwd(g, x, w, out, st);
-        if (t != 0) return t < 0 ? t : 0;
-    }
-    {  // 5x5 stride 2, <= 16 channels: the stem's second conv (down_conv.hip)
-        const int32_t t = isg_s2k5_fwd(g, x, w, out, st);
-        if (t != 0) return t < 0 ? t : 0;
-    }
-    {  // dense spatial conv, <= 48 output channels (tap_conv.hip)
-        const int32_t t = isg_tap_conv(g, x, w, out, false, st);
-        if (t != 0) return t < 0 ? t : 0;
-    }
-    // narrow outputs with spatial taps: LDS halo-tiled kernel (halo_conv.hip)
-    {
-        const int32_t h = isg_halo_conv_fwd(g, x, w, out, st);
-        if (h != 0) return h < 0 ? h : 0;
-    }
+    // the candidates, first taker runs:
+    ISG_TRY(isg_thin_conv(g, x, w, out, false, st));  // thin stride-1 convs on the VALU
+    ISG_TRY(isg_down_conv_fwd(g, x, w, out, st));     // k 2S, stride S: the sub-pixel convT's input gradient
+    ISG_TRY(isg_s2k5_fwd(g, x, w, out, st));          // 5x5 stride 2, <= 16 channels: the stem's second conv
+    ISG_TRY(isg_tap_conv(g, x, w, out, false, st));   // dense spatial conv, <= 48 output channels
+    ISG_TRY(isg_halo_conv_fwd(g, x, w, out, st));     // narrow outputs with spatial taps, LDS halo tiles
+    // else the implicit GEMM below
     if (g->Ci * g->KH * g->KW > kKtabMax)
         return isg_set_error(ISG_ERR_UNSUPPORTED, "conv fwd: K=%d > %d", g->Ci * g->KH * g->KW, kKtabMax);
-    if (int32_t e = check_sinks(out, g->Co, "conv fwd")) return e;
     GemmArgs a{};
     a.src = *x; a.out = *out; a.w = w; a.mode = 0; a.N = g->N;
     a.TH = g->OH; a.TW = g->OW; a.SrcH = g->H; a.SrcW = g->W; a.my = g->SH; a.mx = g->SW;
@@ -316,22 +279,14 @@ int32_t isg_dense_conv_dgrad(const isg_conv_geom* g, const isg_vtensor* dy, cons
     if (vt_channels(dy) != g->Co) return isg_set_error(ISG_ERR_INVALID, "conv dgrad: Co mismatch");
     if (int32_t e = check_sinks(dx, g->Ci, "conv dgrad")) return e;
     if (is_pointwise(g)) return isg_pw_gemm(g, dy, w, dx, true, st);
-    {
-        const int32_t t = isg_thin_conv(g, dy, w, dx, true, st);
-        if (t != 0) return t < 0 ? t : 0;
-    }
-    {  // 5x5 stride 2 as a sub-pixel transposed conv (down_conv.hip)
-        const int32_t t = isg_sub2_dgrad(g, dy, w, dx, st);
-        if (t != 0) return t < 0 ? t : 0;
-    }
-    {
-        const int32_t t = isg_tap_conv(g, dy, w, dx, true, st);
-        if (t != 0) return t < 0 ? t : 0;
-    }
+    // the candidates, first taker runs:
+    ISG_TRY(isg_thin_conv(g, dy, w, dx, true, st));
+    ISG_TRY(isg_sub2_dgrad(g, dy, w, dx, st));  // 5x5 stride 2 as a sub-pixel transposed conv
+    ISG_TRY(isg_tap_conv(g, dy, w, dx, true, st));
+    // else the implicit GEMM below
     if (g->KH > 16 || g->KW > 16) return isg_set_error(ISG_ERR_UNSUPPORTED, "conv dgrad: kernel > 16");
     const int maxk = g->Co * ((g->KH + g->SH - 1) / g->SH) * ((g->KW + g->SW - 1) / g->SW);
     if (maxk > kKtabMax) return isg_set_error(ISG_ERR_UNSUPPORTED, "conv dgrad: K=%d too large", maxk);
-    if (int32_t e = check_sinks(dx, g->Ci, "conv dgrad")) return e;
     GemmArgs a{};
     a.src = *dy; a.out = *dx; a.w = w; a.mode = 1; a.N = g->N;
     a.TH = (g->H + g->SH - 1) / g->SH; a.TW = (g->W + g->SW - 1) / g->SW;

@@ -471,7 +471,7 @@ __global__ __launch_bounds__(kThreads) void sub2_dgrad_lds_kernel(DownArgs a) {
             const int64_t bns = ab ? q.yns : q.ns;
 #pragma unroll
             for (int u = 0; u < 2; ++u)
-                pre[r][u] = *(gcv2_p)((gcfloat_p)(live ? base : a.dy.s[0].p) +  // 16-B aligned (down_src_ok)
+                pre[r][u] = *(gcv2_p)((gcfloat_p)(live ? base : a.dy.s[0].p) +  // 16-B aligned (vt_rows16)
                                       (live ? (int64_t)n * bns + (int64_t)(2 * i + u) * Wd + 2 * joc : 0));
         }
         f32x4 acc[2][2];
@@ -1174,15 +1174,6 @@ bool down_geom(const isg_conv_geom* g, int& S) {
            g->W == S * g->OW && g->W % 4 == 0 && (g->w_ci == 0 || g->w_ci == g->Ci);
 }
 
-bool down_src_ok(const isg_vtensor* v) {
-    for (int i = 0; i < v->nseg; ++i) {
-        const isg_vseg& s = v->s[i];
-        if ((uintptr_t)s.p % 16 || s.n_stride % 4) return false;
-        if (s.xform == ISG_XF_BN_BWD && ((uintptr_t)s.y % 16 || s.y_n_stride % 4)) return false;
-    }
-    return true;
-}
-
 }  // namespace
 
 ISG_STAMP_ACCESSOR(isg_dbg_stamps_down)
@@ -1191,7 +1182,7 @@ ISG_STAMP_ACCESSOR(isg_dbg_stamps_down)
 int32_t isg_down_conv_fwd(const isg_conv_geom* g, const isg_vtensor* src, const float* w,
                           const isg_sinks* out, hipStream_t st) {
     int S = 0;
-    if (!down_geom(g, S) || g->Ci > kMaxC || g->Co > kMaxM || !down_src_ok(src)) return 0;
+    if (!down_geom(g, S) || g->Ci > kMaxC || g->Co > kMaxM || !vt_rows16(*src)) return 0;
     // measured: S = 2 (bottle5_1up's k4 s2, 128^2 cells) ran 15.6 -> 18.2 us here against the
     // halo kernel (too few cells per lane-owned output for the VALU form); S = 4 only
     if (S != 4) return 0;
@@ -1206,8 +1197,7 @@ int32_t isg_down_conv_fwd(const isg_conv_geom* g, const isg_vtensor* src, const 
         if (a.M <= 4) hipLaunchKernelGGL((down_conv_kernel<2, 4>), grid, dim3(kThreads), 0, st, a);
         else hipLaunchKernelGGL((down_conv_kernel<2, 16>), grid, dim3(kThreads), 0, st, a);
     }
-    const int32_t e = isg_check_launch("down_conv_kernel");
-    return e ? e : 1;
+    return launched("down_conv_kernel");
 }
 
 // weight gradient of the stride-S down conv: dy = the conv's OUTPUT gradient (M channels
@@ -1222,8 +1212,8 @@ int32_t isg_down_conv_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const
     a.x = *dy;   // M channels on the cell grid
     a.dy = *x;   // C channels at S x the resolution
     a.dw = dw;
-    a.rep_stride = nrep > 1 ? rep_stride : 0;
-    a.nrep = nrep < 1 ? 1 : nrep;
+    norm_replicas(rep_stride, nrep);
+    a.rep_stride = rep_stride; a.nrep = nrep;
     a.N = g->N; a.M = g->Co; a.C = g->Ci; a.H = g->OH; a.W = g->OW;
     constexpr int TY = 4, TX = 16;
     a.tiles_x = (a.W + TX - 1) / TX;
@@ -1238,35 +1228,29 @@ int32_t isg_down_conv_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const
         if (a.M <= 4) hipLaunchKernelGGL((down_wgrad_kernel<2, 4, TY, TX>), dim3(grid), dim3(kThreads), 0, st, a);
         else hipLaunchKernelGGL((down_wgrad_kernel<2, 16, TY, TX>), dim3(grid), dim3(kThreads), 0, st, a);
     }
-    const int32_t e = isg_check_launch("down_wgrad_kernel");
-    return e ? e : 1;
+    return launched("down_wgrad_kernel");
 }
 
 // Returns 1 if launched, 0 if the shape is not for this kernel, <0 on error.
 int32_t isg_sub2_dgrad(const isg_conv_geom* g, const isg_vtensor* dy, const float* w,
                        const isg_sinks* dx, hipStream_t st) {
-    if (g->groups != 1 || g->SH != 2 || g->SW != 2 || g->KH != 5 || g->KW != 5 ||
-        g->PH != 2 || g->PW != 2 || g->DH != 1 || g->DW != 1 || g->H != 2 * g->OH ||
-        g->W != 2 * g->OW || g->Co > kMaxM || g->Ci > kMaxM || (g->w_ci && g->w_ci != g->Ci))
+    if (!geom_s2k5(g) || g->Co > kMaxM || g->Ci > kMaxM || (g->w_ci && g->w_ci != g->Ci))
         return 0;
     DownArgs a{};
     a.dy = *dy; a.out = *dx; a.w = w;
     a.N = g->N; a.M = g->Ci; a.C = g->Co; a.H = g->OH; a.W = g->OW;
     const dim3 grid((unsigned)((a.W + 63) / 64), (unsigned)((a.H + kRowsPB - 1) / kRowsPB), (unsigned)a.N);
-    if (a.W % 4 || !down_src_ok(dy)) return 0;  // tap_conv's stride-1 phases instead
+    if (a.W % 4 || !vt_rows16(*dy)) return 0;  // tap_conv's stride-1 phases instead
     hipLaunchKernelGGL(sub2_dgrad_lds_kernel, grid, dim3(kThreads), 0, st, a);
-    const int32_t e = isg_check_launch("sub2_dgrad_kernel");
-    return e ? e : 1;
+    return launched("sub2_dgrad_kernel");
 }
 
 // 5x5 stride 2 pad 2 forward with <= 16 input / output channels (s2k5_fwd_kernel).
 // Returns 1 if launched, 0 if the shape is not for this kernel, <0 on error.
 int32_t isg_s2k5_fwd(const isg_conv_geom* g, const isg_vtensor* x, const float* w,
                      const isg_sinks* out, hipStream_t st) {
-    if (g->groups != 1 || g->SH != 2 || g->SW != 2 || g->KH != 5 || g->KW != 5 ||
-        g->PH != 2 || g->PW != 2 || g->DH != 1 || g->DW != 1 || g->H != 2 * g->OH ||
-        g->W != 2 * g->OW || g->W % 4 || g->Co > kMaxM || g->Ci > kMaxM ||
-        (g->w_ci && g->w_ci < g->Ci) || !down_src_ok(x))
+    if (!geom_s2k5(g) || g->W % 4 || g->Co > kMaxM || g->Ci > kMaxM ||
+        (g->w_ci && g->w_ci < g->Ci) || !vt_rows16(*x))
         return 0;
     for (int i = 0; i < x->nseg; ++i)  // the branch-free staging transform: PLAIN / BN_FWD
         if (x->s[i].xform == ISG_XF_BN_BWD) return 0;
@@ -1274,8 +1258,7 @@ int32_t isg_s2k5_fwd(const isg_conv_geom* g, const isg_vtensor* x, const float* 
     S2fArgs a{};
     a.x = *x; a.w = w; a.out = *out;
     a.st16 = out->nsink == 1 && out->s[0].mode == ISG_SINK_STORE && out->s[0].c0 == 0 &&
-             out->s[0].C == g->Co && g->OW % 4 == 0 && (uintptr_t)out->s[0].p % 16 == 0 &&
-             out->s[0].n_stride % 4 == 0;
+             out->s[0].C == g->Co && g->OW % 4 == 0 && sinks_rows16(*out);
     a.N = g->N; a.M = g->Co; a.C = g->Ci; a.wc = g->w_ci ? g->w_ci : g->Ci; a.OH = g->OH; a.OW = g->OW;
     const int G = (a.C + 3) / 4;
     if (a.wc > (G == 4 ? 16 : kS2fMaxWc)) return 0;  // the whole-weight copy's bound
@@ -1284,14 +1267,7 @@ int32_t isg_s2k5_fwd(const isg_conv_geom* g, const isg_vtensor* x, const float* 
     const int64_t nt = (int64_t)a.N * a.tiles_x * a.tiles_y;
     if (nt >= (1ll << 31)) return 0;
     a.ntiles = (int)nt;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-    }
-    const int target = cus;  // one 8-wave workgroup per CU (LDS 2 x 52 KB + 8 KB)
+    const int target = isg_cu_count();  // one 8-wave workgroup per CU (LDS 2 x 52 KB + 8 KB)
     a.tpw = (int)std::max<int64_t>(1, (nt + target - 1) / target);
     const int grid = (int)((nt + a.tpw - 1) / a.tpw);
     // two bands + the four consumer waves' output rows (st16 epilogue)
@@ -1305,18 +1281,15 @@ int32_t isg_s2k5_fwd(const isg_conv_geom* g, const isg_vtensor* x, const float* 
         attr[G] = true;
     }
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(2 * kThreads), lds, st, a);
-    const int32_t e = isg_check_launch("s2k5_fwd_kernel");
-    return e ? e : 1;
+    return launched("s2k5_fwd_kernel");
 }
 
 // 5x5 stride 2 pad 2 weight gradient with <= 16 input / output channels (s2k5_wgrad_kernel).
 // Returns 1 if launched, 0 if the shape is not for this kernel, <0 on error.
 int32_t isg_s2k5_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x,
                        double* dw, double* dbias, int64_t rep_stride, int32_t nrep, hipStream_t st) {
-    if (g->groups != 1 || g->SH != 2 || g->SW != 2 || g->KH != 5 || g->KW != 5 ||
-        g->PH != 2 || g->PW != 2 || g->DH != 1 || g->DW != 1 || g->H != 2 * g->OH ||
-        g->W != 2 * g->OW || g->OW % 4 || g->Co > kMaxM || g->Ci > kMaxM ||
-        (g->w_ci && g->w_ci < g->Ci) || !down_src_ok(x) || !down_src_ok(dy))
+    if (!geom_s2k5(g) || g->OW % 4 || g->Co > kMaxM || g->Ci > kMaxM ||
+        (g->w_ci && g->w_ci < g->Ci) || !vt_rows16(*x) || !vt_rows16(*dy))
         return 0;
     // the kernel's branch-free transforms: x PLAIN / BN_FWD with any activation, dy PLAIN /
     // BN_BWD without one
@@ -1327,22 +1300,15 @@ int32_t isg_s2k5_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_
     if ((int64_t)g->H * g->W >= (1ll << 31)) return 0;
     S2wArgs a{};
     a.dy = *dy; a.x = *x; a.dw = dw; a.dbias = dbias;
-    a.rep_stride = nrep > 1 ? rep_stride : 0;
-    a.nrep = nrep < 1 ? 1 : nrep;
+    norm_replicas(rep_stride, nrep);
+    a.rep_stride = rep_stride; a.nrep = nrep;
     a.N = g->N; a.M = g->Co; a.C = g->Ci; a.wc = g->w_ci ? g->w_ci : g->Ci; a.OH = g->OH; a.OW = g->OW;
     a.tiles_x = (a.OW + kWgX - 1) / kWgX;
     a.tiles_y = (a.OH + kWgRows - 1) / kWgRows;
     const int64_t nt = (int64_t)a.N * a.tiles_x * a.tiles_y;
     if (nt >= (1ll << 31)) return 0;
     a.ntiles = (int)nt;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-    }
-    const int target = cus;  // one 8-wave workgroup per CU (LDS 2 x 60 KB)
+    const int target = isg_cu_count();  // one 8-wave workgroup per CU (LDS 2 x 60 KB)
     a.tpw = (int)std::max<int64_t>(1, (nt + target - 1) / target);
     const int grid = (int)((nt + a.tpw - 1) / a.tpw);
     bool yb = false;
@@ -1359,6 +1325,5 @@ int32_t isg_s2k5_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_
         attr[ki] = true;
     }
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(2 * kThreads), lds, st, a);
-    const int32_t e = isg_check_launch("s2k5_wgrad_kernel");
-    return e ? e : 1;
+    return launched("s2k5_wgrad_kernel");
 }

@@ -250,6 +250,5 @@ int32_t isg_halo_conv_fwd(const isg_conv_geom* g, const isg_vtensor* x, const fl
         else HALO_LAUNCH(2, 2);
     }
 #undef HALO_LAUNCH
-    const int32_t e = isg_check_launch("halo_conv_kernel");
-    return e ? e : 1;
+    return launched("halo_conv_kernel");
 }

@@ -807,14 +807,7 @@ int32_t pwx_launch(const PwxArgs& a, dim3 grid, int lds, hipStream_t st) {
 
 template <int BP, bool HY, bool SEG1, bool RES>
 int32_t pwx_dispatch(const PwxArgs& a, dim3 grid, int lds, int tpw, hipStream_t st) {
-    switch (tpw) {
-        case 1: return pwx_launch<1, BP, HY, SEG1, RES>(a, grid, lds, st);
-        case 2: return pwx_launch<2, BP, HY, SEG1, RES>(a, grid, lds, st);
-        case 3: return pwx_launch<3, BP, HY, SEG1, RES>(a, grid, lds, st);
-        case 4: return pwx_launch<4, BP, HY, SEG1, RES>(a, grid, lds, st);
-        case 5: case 6: return pwx_launch<6, BP, HY, SEG1, RES>(a, grid, lds, st);
-        default: return pwx_launch<8, BP, HY, SEG1, RES>(a, grid, lds, st);
-    }
+    return with_tpw(tpw, [&](auto T) { return pwx_launch<decltype(T)::value, BP, HY, SEG1, RES>(a, grid, lds, st); });
 }
 template <int BP, bool HY>
 int32_t pwx_dispatch_seg(const PwxArgs& a, dim3 grid, int lds, int tpw, bool seg1, hipStream_t st) {
@@ -831,39 +824,8 @@ int pwx_wrow_quads(int wmode, int BM, int Kp) {
     return p;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// host mirrors of stage.h vt_fast / sinks_fast
-bool host_seg_fast(const isg_vseg& s) {
-    if (s.xform == ISG_XF_BN_FWD || s.xform == ISG_XF_BN_BWD) return s.bn.coef || s.bn.train;
-    return true;
-}
-bool host_vt_fast(const isg_vtensor& v) {
-    for (int s = 0; s < v.nseg; ++s)
-        if (!host_seg_fast(v.s[s])) return false;
-    return true;
-}
-bool host_sinks_fast(const isg_sinks& sk) {
-    for (int s = 0; s < sk.nsink; ++s) {
-        const isg_sink& k = sk.s[s];
-        if (k.mode == ISG_SINK_ACTBWD && !(k.bn.coef || k.bn.train)) return false;
-    }
-    return true;
-}
-
-// The slab path needs every source channel row 16-B aligned (HW % 4, n_stride % 4, base).
-bool pwx_src_ok(const isg_vtensor& v, int HW) {
-    if (HW % 4) return false;
-    for (int s = 0; s < v.nseg; ++s) {
-        const isg_vseg& g = v.s[s];
-        if (!aligned16(g.p) || g.n_stride % 4) return false;
-        if ((g.xform == ISG_XF_BN_BWD || g.xform == ISG_XF_BN_FWD) && g.y &&
-            (!aligned16(g.y) || g.y_n_stride % 4))
-            return false;
-    }
-    if (v.mat && (!aligned16(v.mat) || v.mat_n_stride % 4)) return false;
-    return true;
-}
+// The slab path and the thin kernels need every source channel row 16-B aligned.
+bool pwx_src_ok(const isg_vtensor& v, int HW) { return HW % 4 == 0 && vt_rows16(v); }
 
 
 // ---- thin pointwise (K, M <= 16) on the VALU ---------------------------------------------
@@ -1019,33 +981,19 @@ __global__ __launch_bounds__(64 * kThinWaves) void thin_pw_kernel(ThinPwArgs a) 
     }
 }
 
-bool sinks_aligned16(const isg_sinks& sk) {
-    for (int s = 0; s < sk.nsink; ++s) {
-        const isg_sink& k = sk.s[s];
-        if (k.mode == ISG_SINK_NONE) continue;
-        if (!aligned16(k.p) || k.n_stride % 4) return false;
-        if (k.mode == ISG_SINK_ACTBWD && (!aligned16(k.y) || k.y_n_stride % 4)) return false;
-    }
-    return true;
-}
-
 // 1: launched, 0: not applicable, < 0: error
 int32_t thin_pw(const PwArgs& a, hipStream_t st) {
-    if (a.HW % 4 || !pwx_src_ok(a.src, a.HW) || !sinks_aligned16(a.out))
-        return 0;
+    if (!pwx_src_ok(a.src, a.HW) || !sinks_rows16(a.out)) return 0;
     ThinPwArgs b{};
     b.src = a.src; b.out = a.out; b.w = a.w; b.rs = a.rs; b.cs = a.cs; b.HW = a.HW;
     b.Q = a.P / 4;
     const dim3 grid((unsigned)((b.Q + 64 * kThinWaves - 1) / (64 * kThinWaves)));
-    bool pre = false;
-    for (int s = 0; s < a.out.nsink; ++s)
-        pre |= a.out.s[s].mode == ISG_SINK_ACTBWD || a.out.s[s].mode == ISG_SINK_ACCUM;
+    const bool pre = sinks_read_operand(a.out);
 #define ISG_THIN_PW(KK, MM)                                                                      \
     if (a.K == KK && a.M == MM) {                                                                 \
         if (pre) hipLaunchKernelGGL((thin_pw_kernel<KK, MM, true>), grid, dim3(64 * kThinWaves), 0, st, b); \
         else hipLaunchKernelGGL((thin_pw_kernel<KK, MM, false>), grid, dim3(64 * kThinWaves), 0, st, b); \
-        const int32_t e = isg_check_launch("thin_pw_kernel");                                    \
-        return e ? e : 1;                                                                        \
+        return launched("thin_pw_kernel");                                                       \
     }
     ISG_THIN_PW(4, 16)
     ISG_THIN_PW(16, 4)
@@ -1080,12 +1028,7 @@ int32_t isg_pw_gemm(const isg_conv_geom* g, const isg_vtensor* src, const float*
     // a folded residual tail (isg.h: BN_FWD segment with y / vtensor.mat in the forward,
     // ACTBWD sink's residual form in the input gradient) runs on the slab kernel only
     const bool rbn_src = src->rbn.stats || src->rbn.coef;
-    bool res_in = src->mat != nullptr || rbn_src, res_out = false;
-    for (int s = 0; s < src->nseg; ++s) res_in |= src->s[s].xform == ISG_XF_BN_FWD && src->s[s].y;
-    for (int s = 0; s < out->nsink; ++s) {
-        const isg_sink& k = out->s[s];
-        res_out |= k.r || k.old || k.p2 || k.rbn.stats || k.rbn.coef;
-    }
+    const bool res_in = isg_vt_res(src), res_out = isg_sinks_res(out);
     const bool res = res_in || res_out;
     // forward: one source segment (the residual's own BatchNorm: also one sink), any sinks;
     // input gradient: one residual sink, any gradient segments (a stacked pair's two)
@@ -1095,8 +1038,7 @@ int32_t isg_pw_gemm(const isg_conv_geom* g, const isg_vtensor* src, const float*
         return isg_set_error(ISG_ERR_UNSUPPORTED, "pw gemm: residual forms need one segment in the forward "
                              "(input residual), one ACTBWD residual sink in the input gradient");
     if (!res) {  // thin layers (K, M <= 16) on the VALU
-        const int32_t t = thin_pw(a, st);
-        if (t != 0) return t < 0 ? t : 0;
+        ISG_TRY(thin_pw(a, st));
     }
     int wmode = 0;
     if (aligned16(w)) {
@@ -1121,23 +1063,13 @@ int32_t isg_pw_gemm(const isg_conv_geom* g, const isg_vtensor* src, const float*
         b.src = a.src; b.out = a.out; b.w = w; b.rs = a.rs; b.cs = a.cs;
         b.HW = a.HW; b.M = a.M; b.K = a.K; b.Kp = (a.K + 15) / 16 * 16; b.P = a.P;
         b.wmode = wmode;
-        b.fast = host_vt_fast(*src) && host_sinks_fast(*out);
-        b.pre_on = 0;
+        b.fast = vt_fast(*src) && sinks_fast(*out);
+        b.pre_on = sinks_read_operand(*out);
+        b.stat_on = vt_stat_on(*src) || sinks_stat_on(*out);
         b.res_on = res_out ? 1 : 0;
         auto bn_on = [](const isg_bn& q) { return q.stats != nullptr || q.coef != nullptr; };
         b.rbn_in = res_in && bn_on(src->rbn) ? 1 : 0;
         b.rbn_out = res_out && bn_on(out->s[0].rbn) ? 1 : 0;
-        for (int s = 0; s < out->nsink; ++s)
-            if (out->s[s].mode == ISG_SINK_ACTBWD || out->s[s].mode == ISG_SINK_ACCUM) b.pre_on = 1;
-        b.stat_on = 0;
-        for (int s = 0; s < src->nseg; ++s) {
-            const isg_vseg& g = src->s[s];
-            if ((g.xform == ISG_XF_BN_FWD || g.xform == ISG_XF_BN_BWD) && !g.bn.coef && g.bn.stats) b.stat_on = 1;
-        }
-        for (int s = 0; s < out->nsink; ++s) {
-            const isg_sink& k = out->s[s];
-            if (k.mode == ISG_SINK_ACTBWD && !k.bn.coef && k.bn.stats) b.stat_on = 1;
-        }
         // HY also selects the 4-group statistics loads (coef_issue<4>): a BN_BWD segment
         // finalised by the consumer needs them even when its y is its own input (ADVICE r03:
         // the 2-group form would apply identity coefficients there)
@@ -1218,13 +1150,6 @@ int32_t isg_pw_gemm(const isg_conv_geom* g, const isg_vtensor* src, const float*
     const int tpw = bm / 16;  // (bm/16 row tiles * 4 pixel tiles) / 4 waves
     dim3 grid((unsigned)pblocks, (unsigned)((a.M + bm - 1) / bm));
     // template tile count >= tpw; surplus tiles compute on unused rows, never stored
-    switch (tpw) {
-        case 1: hipLaunchKernelGGL(pw_kernel<1>, grid, dim3(kThreads), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(pw_kernel<2>, grid, dim3(kThreads), 0, st, a); break;
-        case 3: hipLaunchKernelGGL(pw_kernel<3>, grid, dim3(kThreads), 0, st, a); break;
-        case 4: hipLaunchKernelGGL(pw_kernel<4>, grid, dim3(kThreads), 0, st, a); break;
-        case 5: case 6: hipLaunchKernelGGL(pw_kernel<6>, grid, dim3(kThreads), 0, st, a); break;
-        default: hipLaunchKernelGGL(pw_kernel<8>, grid, dim3(kThreads), 0, st, a); break;
-    }
+    with_tpw(tpw, [&](auto T) { hipLaunchKernelGGL(pw_kernel<decltype(T)::value>, grid, dim3(kThreads), 0, st, a); });
     return isg_check_launch("pw_kernel");
 }

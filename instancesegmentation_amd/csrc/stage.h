@@ -287,20 +287,21 @@ ISG_DEV void sink_row_apply(const SinkRow& q, int n, int64_t pix, float v, float
 // "fast" = every record comes from plain branch-free loads: finalised coefficients, or
 // (training mode) the statistics replicas evaluated in coef_finish / sink_finish
 // (consumer-side finalisation). Eval mode (running statistics) takes the slow path.
-ISG_DEV bool seg_fast(const isg_vseg& s) {
+// Host and device: the launchers choose an instantiation by the kernels' own definition.
+ISG_HD bool seg_fast(const isg_vseg& s) {
     if (s.xform == ISG_XF_BN_FWD || s.xform == ISG_XF_BN_BWD) return s.bn.coef || s.bn.train;
     return true;
 }
-ISG_DEV bool vt_fast(const isg_vtensor& v) {
+ISG_HD bool vt_fast(const isg_vtensor& v) {
     bool ok = seg_fast(v.s[0]);
     if (v.nseg > 1) ok = ok && seg_fast(v.s[1]);
     if (v.nseg > 2) ok = ok && seg_fast(v.s[2]);
     return ok;
 }
-ISG_DEV bool sink_fast(const isg_sink& k) {
+ISG_HD bool sink_fast(const isg_sink& k) {
     return k.mode != ISG_SINK_ACTBWD || k.bn.coef || k.bn.train;
 }
-ISG_DEV bool sinks_fast(const isg_sinks& sk) {
+ISG_HD bool sinks_fast(const isg_sinks& sk) {
     bool ok = sink_fast(sk.s[0]);
     if (sk.nsink > 1) ok = ok && sink_fast(sk.s[1]);
     if (sk.nsink > 2) ok = ok && sink_fast(sk.s[2]);

@@ -394,13 +394,7 @@ __global__ __launch_bounds__(kThreads) void tap_conv_kernel(TapArgs a) {
 
 template <int MT, int G, bool YB, bool PAIR>
 int32_t tap_launch(const TapArgs& a, size_t lds, hipStream_t st) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-    }
+    const int cus = isg_cu_count();
     auto k = tap_conv_kernel<MT, G, YB, PAIR>;
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -543,9 +537,7 @@ int32_t isg_tap_conv(const isg_conv_geom* g, const isg_vtensor* src, const float
     for (int i = 0; i < src->nseg; ++i) yb |= src->s[i].xform == ISG_XF_BN_BWD;
     const size_t lds = (size_t)(a.ws_floats + 4 * a.CHS) * sizeof(float);
     const bool pair = mx == 2;
-    int32_t e;
-    if (mt == 1) e = tap_launch_g<1>(a, lds, G, yb, pair, st);
-    else if (mt == 2) e = tap_launch_g<2>(a, lds, G, yb, pair, st);
-    else e = tap_launch_g<3>(a, lds, G, yb, pair, st);
-    return e ? e : 1;
+    if (mt == 1) return launched(tap_launch_g<1>(a, lds, G, yb, pair, st));
+    if (mt == 2) return launched(tap_launch_g<2>(a, lds, G, yb, pair, st));
+    return launched(tap_launch_g<3>(a, lds, G, yb, pair, st));
 }

@@ -248,13 +248,7 @@ __global__ __launch_bounds__(kThreads) void tap_wgrad_kernel(TwArgs a) {
 
 template <int NT, bool YB, bool PAIR>
 int32_t tw_launch(const TwArgs& a, int nchunk, size_t lds, hipStream_t st) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-    }
+    const int cus = isg_cu_count();
     auto k = tap_wgrad_kernel<NT, YB, PAIR>;
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -574,13 +568,7 @@ __global__ __launch_bounds__(kThreads, 2) void tap_wgrad_all_kernel(TwaArgs a) {
 
 template <int NTW>
 int32_t twa_launch(const TwaArgs& a, size_t lds, bool yb, hipStream_t st) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-    }
+    const int cus = isg_cu_count();
     auto k = yb ? tap_wgrad_all_kernel<NTW, true> : tap_wgrad_all_kernel<NTW, false>;
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -729,17 +717,15 @@ int32_t twa_try(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor
     a.m_bx = magic(a.BX);
     a.m_hrp = (uint32_t)(((1ull << 32) + a.HRP - 1) / a.HRP);  // k < 4*kTwaMaxPW: exact
     a.dy = *dy; a.x = *x; a.dw = dw; a.dbias = dbias;
-    a.rep_stride = nrep > 1 ? rep_stride : 0;
-    a.nrep = nrep < 1 ? 1 : nrep;
+    norm_replicas(rep_stride, nrep);
+    a.rep_stride = rep_stride; a.nrep = nrep;
     const size_t lds = (size_t)(a.C * a.CHS + 16 * a.DQ) * sizeof(float);
     bool yb = false;
     for (int i = 0; i < dy->nseg; ++i) yb |= dy->s[i].xform == ISG_XF_BN_BWD;
-    int32_t e;
-    if (NTW <= 4) e = twa_launch<4>(a, lds, yb, st);
-    else if (NTW <= 6) e = twa_launch<6>(a, lds, yb, st);
-    else if (NTW <= 7) e = twa_launch<7>(a, lds, yb, st);
-    else e = twa_launch<8>(a, lds, yb, st);
-    return e ? e : 1;
+    if (NTW <= 4) return launched(twa_launch<4>(a, lds, yb, st));
+    if (NTW <= 6) return launched(twa_launch<6>(a, lds, yb, st));
+    if (NTW <= 7) return launched(twa_launch<7>(a, lds, yb, st));
+    return launched(twa_launch<8>(a, lds, yb, st));
 }
 
 }  // namespace
@@ -763,8 +749,8 @@ int32_t isg_tap_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_v
     if ((int64_t)g->H * g->W * 4 >= (1ll << 31) || (int64_t)g->OH * g->OW * 4 >= (1ll << 31)) return 0;
     TwArgs a{};
     a.dy = *dy; a.x = *x; a.dw = dw; a.dbias = dbias;
-    a.rep_stride = nrep > 1 ? rep_stride : 0;
-    a.nrep = nrep < 1 ? 1 : nrep;
+    norm_replicas(rep_stride, nrep);
+    a.rep_stride = rep_stride; a.nrep = nrep;
     a.N = g->N; a.C = g->Ci; a.Co = g->Co; a.H = g->H; a.W = g->W; a.OH = g->OH; a.OW = g->OW;
     a.WC = g->w_ci > 0 ? g->w_ci : g->Ci;
     a.KH = g->KH; a.KW = g->KW; a.SH = g->SH; a.SW = g->SW; a.PH = g->PH; a.PW = g->PW;
@@ -801,14 +787,6 @@ int32_t isg_tap_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_v
     bool yb = false;
     for (int i = 0; i < dy->nseg; ++i) yb |= dy->s[i].xform == ISG_XF_BN_BWD;
     const bool pair = mx == 2;
-    int32_t e;
-    switch (NT) {
-        case 1: e = tw_launch_v<1>(a, nchunk, lds, yb, pair, st); break;
-        case 2: e = tw_launch_v<2>(a, nchunk, lds, yb, pair, st); break;
-        case 3: e = tw_launch_v<3>(a, nchunk, lds, yb, pair, st); break;
-        case 4: e = tw_launch_v<4>(a, nchunk, lds, yb, pair, st); break;
-        case 6: e = tw_launch_v<6>(a, nchunk, lds, yb, pair, st); break;
-        default: e = tw_launch_v<8>(a, nchunk, lds, yb, pair, st); break;
-    }
-    return e ? e : 1;
+    // NT: 1, 2, 3, 4, 6 or 8 (tw_layout)
+    return launched(with_tpw(NT, [&](auto T) { return tw_launch_v<decltype(T)::value>(a, nchunk, lds, yb, pair, st); }));
 }

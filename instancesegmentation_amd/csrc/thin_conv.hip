@@ -315,26 +315,19 @@ int32_t isg_thin_conv(const isg_conv_geom* g, const isg_vtensor* src, const floa
     // 4 pixels per lane: 3x3 / pad 1 / dilation 1, same plane size, 16-B aligned rows
     const bool x4 = K == 3 && a.P == 1 && a.D == 1 && a.DstW % 4 == 0 && a.SrcW == a.DstW &&
                     a.SrcH == a.DstH;
-    bool aligned = true;
-    for (int i = 0; i < src->nseg; ++i)
-        aligned &= ((uintptr_t)src->s[i].p % 16 == 0) && src->s[i].n_stride % 4 == 0 &&
-                   (src->s[i].xform != ISG_XF_BN_BWD ||
-                    ((uintptr_t)src->s[i].y % 16 == 0 && src->s[i].y_n_stride % 4 == 0));
-    if (x4 && aligned) {
+    if (x4 && vt_rows16(*src)) {
         dim3 g4((unsigned)((P / 4 + kThreads - 1) / kThreads));
         if (C == 4 && M == 1) hipLaunchKernelGGL((thin_conv3_x4_kernel<4, 1>), g4, dim3(kThreads), 0, st, a);
         else if (C == 1 && M == 4) hipLaunchKernelGGL((thin_conv3_x4_kernel<1, 4>), g4, dim3(kThreads), 0, st, a);
         else if (C == 4 && M == 4) hipLaunchKernelGGL((thin_conv3_x4_kernel<4, 4>), g4, dim3(kThreads), 0, st, a);
         else return 0;
-        const int32_t e = isg_check_launch("thin_conv3_x4_kernel");
-        return e ? e : 1;
+        return launched("thin_conv3_x4_kernel");
     }
     if (C == 4 && M == 1 && K == 3) hipLaunchKernelGGL((thin_conv_kernel<4, 1, 3>), grid, dim3(kThreads), 0, st, a);
     else if (C == 1 && M == 4 && K == 3) hipLaunchKernelGGL((thin_conv_kernel<1, 4, 3>), grid, dim3(kThreads), 0, st, a);
     else if (C == 4 && M == 4 && K == 3) hipLaunchKernelGGL((thin_conv_kernel<4, 4, 3>), grid, dim3(kThreads), 0, st, a);
     else return 0;
-    const int32_t e = isg_check_launch("thin_conv_kernel");
-    return e ? e : 1;
+    return launched("thin_conv_kernel");
 }
 
 // Returns 1 if launched, 0 if the shape is not for this kernel, <0 on error.
@@ -344,15 +337,11 @@ int32_t isg_thin_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_
         g->PH != 1 || g->PW != 1 || g->DH != 1 || g->DW != 1 || g->OH != g->H || g->OW != g->W ||
         g->W % 4 || dy->nseg != 1 || x->nseg != 1 || (g->w_ci > 0 && g->w_ci != g->Ci))
         return 0;
-    auto al = [](const isg_vseg& sg) {
-        return (uintptr_t)sg.p % 16 == 0 && sg.n_stride % 4 == 0 &&
-               (sg.xform != ISG_XF_BN_BWD || ((uintptr_t)sg.y % 16 == 0 && sg.y_n_stride % 4 == 0));
-    };
-    if (!al(dy->s[0]) || !al(x->s[0])) return 0;
+    if (!vt_rows16(*dy) || !vt_rows16(*x)) return 0;
     ThinWgArgs a{};
     a.dy = *dy; a.x = *x; a.dw = dw; a.dbias = dbias;
-    a.rep_stride = nrep > 1 ? rep_stride : 0;
-    a.nrep = nrep < 1 ? 1 : nrep;
+    norm_replicas(rep_stride, nrep);
+    a.rep_stride = rep_stride; a.nrep = nrep;
     a.N = g->N; a.H = g->H; a.W = g->W;
     const int64_t nq = (int64_t)g->N * g->H * (g->W / 4);
     // ~4 quads per lane: enough work per workgroup to amortise its reduction
@@ -363,6 +352,5 @@ int32_t isg_thin_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_
         hipLaunchKernelGGL((thin_wgrad3_x4_kernel<1, 4>), dim3((unsigned)blocks), dim3(kThreads), 0, st, a);
     else
         return 0;
-    const int32_t e = isg_check_launch("thin_wgrad3_x4_kernel");
-    return e ? e : 1;
+    return launched("thin_wgrad3_x4_kernel");
 }

@@ -530,32 +530,10 @@ __global__ __launch_bounds__(kThreads) void pwg_group_kernel(PwgArgs p0, PwgArgs
     }
 }
 
-bool g_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-bool pwg_src_ok(const isg_vtensor& v, int HW) {
-    if (HW % 4) return false;
-    for (int s = 0; s < v.nseg; ++s) {
-        const isg_vseg& g = v.s[s];
-        if (!g_aligned16(g.p) || g.n_stride % 4) return false;
-        if (g.xform == ISG_XF_BN_BWD && g.y && (!g_aligned16(g.y) || g.y_n_stride % 4)) return false;
-    }
-    return true;
-}
-
 bool pwg_has_y(const isg_vtensor& v) {
     for (int s = 0; s < v.nseg; ++s)
         if (v.s[s].xform == ISG_XF_BN_BWD && v.s[s].y && v.s[s].y != v.s[s].p) return true;
     return false;
-}
-
-bool pwg_fast(const isg_vtensor& v) {
-    for (int s = 0; s < v.nseg; ++s) {
-        const isg_vseg& g = v.s[s];
-        // stage.h seg_fast: finalised coefficients or training-mode statistics
-        if ((g.xform == ISG_XF_BN_FWD || g.xform == ISG_XF_BN_BWD) && !(g.bn.coef || g.bn.train))
-            return false;
-    }
-    return true;
 }
 
 template <int TPW, int NU, bool HY>
@@ -827,14 +805,9 @@ int32_t pwk_try(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor
     PwkArgs a{};
     a.dy = *dy; a.x = *x; a.dw = dw; a.dbias = dbias; a.rep_stride = rep_stride; a.nrep = nrep;
     a.HW = HW; a.R = g->Co; a.C = g->Ci; a.P = P;
-    a.fast = pwg_fast(*dy) && pwg_fast(*x);
+    a.fast = vt_fast(*dy) && vt_fast(*x);
     if (!a.fast) return 0;  // eval-mode statistics (direct ABI calls): pwg_kernel's fp64 path
-    a.stat_on = 0;
-    for (const isg_vtensor* v : {dy, x})
-        for (int s = 0; s < v->nseg; ++s) {
-            const isg_vseg& q = v->s[s];
-            if ((q.xform == ISG_XF_BN_FWD || q.xform == ISG_XF_BN_BWD) && !q.bn.coef && q.bn.stats) a.stat_on = 1;
-        }
+    a.stat_on = vt_stat_on(*dy) || vt_stat_on(*x);
     const bool hy = pwg_has_y(*dy);
     // block shape: the fewest slab rows loaded per super-tile over the whole dW
     static const int shapes[6][2] = {{1, 3}, {3, 1}, {2, 2}, {1, 2}, {2, 1}, {1, 1}};
@@ -861,10 +834,9 @@ int32_t pwk_try(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor
     ISG_PWK_CASE(1, 3) ISG_PWK_CASE(3, 1) ISG_PWK_CASE(2, 2) ISG_PWK_CASE(1, 2) ISG_PWK_CASE(2, 1)
     rc = hy ? pwk_launch<1, 1, true>(a, grid, st) : pwk_launch<1, 1, false>(a, grid, st);
 #undef ISG_PWK_CASE
-    return rc ? rc : 1;
+    return launched(rc);
 }
 
-// returns 1 when launched, 0 when the shape is not for this kernel, <0 on error
 // a pwg launch, planned: its record, grid, dynamic LDS and instantiation
 struct PwgPlan {
     PwgArgs a;
@@ -875,26 +847,24 @@ struct PwgPlan {
     int key() const { return 1 + (tpw * 16 + nu) * 2 + (hy ? 1 : 0); }
 };
 
-// the shape and operand checks of pwg_try and the launch geometry; false: not for pwg
+// the 1x1 weight-gradient kernels' (pwk, pwg) shape and operand checks: the per-op route
+// (pwg_try) and the executor's grouping (isg_pwg_plan) refuse the same ops
+bool pwg_applies(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x) {
+    return geom_1x1_s1(g) && g->OH == g->H && g->OW == g->W && g->Co >= 2 &&
+           (g->H * g->W) % 4 == 0 && vt_rows16(*dy) && vt_rows16(*x);
+}
+
+// the launch geometry of an op that pwg_applies to; false: not for pwg (grid too large)
 bool pwg_plan(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x, double* dw,
               double* dbias, int64_t rep_stride, int32_t nrep, PwgPlan& pl) {
-    if (!(g->KH == 1 && g->KW == 1 && g->SH == 1 && g->SW == 1 && g->PH == 0 && g->PW == 0))
-        return false;
-    if (g->OH != g->H || g->OW != g->W || g->Co < 2) return false;
     const int HW = g->H * g->W;
-    if (!pwg_src_ok(*dy, HW) || !pwg_src_ok(*x, HW)) return false;
     PwgArgs& a = pl.a;
     a = PwgArgs{};
     a.dy = *dy; a.x = *x; a.dw = dw; a.dbias = dbias; a.rep_stride = rep_stride; a.nrep = nrep;
     a.HW = HW; a.R = g->Co; a.C = g->Ci;
     a.P = (int64_t)g->N * HW;
-    a.fast = pwg_fast(*dy) && pwg_fast(*x);
-    a.stat_on = 0;
-    for (const isg_vtensor* v : {dy, x})
-        for (int s = 0; s < v->nseg; ++s) {
-            const isg_vseg& q = v->s[s];
-            if ((q.xform == ISG_XF_BN_FWD || q.xform == ISG_XF_BN_BWD) && !q.bn.coef && q.bn.stats) a.stat_on = 1;
-        }
+    a.fast = vt_fast(*dy) && vt_fast(*x);
+    a.stat_on = vt_stat_on(*dy) || vt_stat_on(*x);
     pl.hy = pwg_has_y(*dy) || pwg_has_y(*x);
     a.ntiles = (a.P + kGTP - 1) / kGTP;
     int br = std::min(64, (a.R + 15) / 16 * 16);
@@ -919,8 +889,7 @@ bool pwg_plan(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* 
     a.off_k = (kThreads * (int)sizeof(ChSrc) + 15) & ~15;
     a.off_x = (a.off_k + kGMaxRows * (int)(sizeof(ChanCoef) + 2 * sizeof(float)) + 15) & ~15;
     pl.lds = (size_t)a.off_x + (size_t)(br + bc) * kGS * sizeof(float);
-    const int tpw = ((br / 16) * (bc / 16) + 3) / 4;
-    pl.tpw = tpw <= 4 ? tpw : tpw <= 6 ? 6 : 8;
+    pl.tpw = with_tpw(((br / 16) * (bc / 16) + 3) / 4, [](auto T) { return (int)decltype(T)::value; });
     pl.grid = dim3((unsigned)gx, (unsigned)gy);
     const int passes = (br + bc + 15) / 16;
     pl.nu = passes <= 4 ? 4 : passes <= 8 ? 8 : 12;
@@ -978,41 +947,17 @@ int32_t pwg_run(const PwgPlan* const* pl, int n, hipStream_t st) {
 // returns 1 when launched, 0 when the shape is not for this kernel, <0 on error
 int32_t pwg_try(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x, double* dw,
                 double* dbias, int64_t rep_stride, int32_t nrep, hipStream_t st) {
-    {
-        if (!(g->KH == 1 && g->KW == 1 && g->SH == 1 && g->SW == 1 && g->PH == 0 && g->PW == 0))
-            return 0;
-        if (g->OH != g->H || g->OW != g->W || g->Co < 2) return 0;
-        const int HW = g->H * g->W;
-        if (!pwg_src_ok(*dy, HW) || !pwg_src_ok(*x, HW)) return 0;
-        if (const int32_t k = pwk_try(g, dy, x, dw, dbias, rep_stride, nrep, st)) return k;
-    }
+    if (!pwg_applies(g, dy, x)) return 0;
+    if (const int32_t k = pwk_try(g, dy, x, dw, dbias, rep_stride, nrep, st)) return k;
     PwgPlan pl;
     if (!pwg_plan(g, dy, x, dw, dbias, rep_stride, nrep, pl)) return 0;
     const PwgPlan* p = &pl;
-    const int32_t rc = pwg_run(&p, 1, st);
-    return rc ? rc : 1;
-}
-
-int vt_channels(const isg_vtensor* v) {
-    int c = 0;
-    for (int i = 0; i < v->nseg; ++i) c += v->s[i].C;
-    return c;
+    return launched(pwg_run(&p, 1, st));
 }
 
 }  // namespace
 
 ISG_STAMP_ACCESSOR(isg_dbg_stamps_wgrad)
-
-int32_t isg_tap_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x, double* dw,
-                      double* dbias, int64_t rep_stride, int32_t nrep, hipStream_t st);
-
-int32_t isg_thin_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x, double* dw,
-                       double* dbias, int64_t rep_stride, int32_t nrep, hipStream_t st);
-int32_t isg_down_conv_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x,
-                            double* dw, double* dbias, int64_t rep_stride, int32_t nrep,
-                            hipStream_t st);
-int32_t isg_s2k5_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x,
-                       double* dw, double* dbias, int64_t rep_stride, int32_t nrep, hipStream_t st);
 
 int32_t isg_dense_conv_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, const isg_vtensor* x,
                              double* dw, double* dbias, int64_t rep_stride, int32_t nrep,
@@ -1020,20 +965,15 @@ int32_t isg_dense_conv_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, cons
     if (vt_channels(dy) != g->Co || vt_channels(x) != g->Ci)
         return isg_set_error(ISG_ERR_INVALID, "conv wgrad: channel mismatch");
     if (!dw) return isg_set_error(ISG_ERR_INVALID, "conv wgrad: dw is NULL");
-    if (!(g->KH == 1 && g->KW == 1)) {  // thin 3x3 (thin_conv.hip), narrow spatial (tap_wgrad.hip)
-        int32_t t = isg_thin_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st);
-        if (t != 0) return t < 0 ? t : 0;
-        t = isg_down_conv_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st);  // convT weights
-        if (t != 0) return t < 0 ? t : 0;
-        t = isg_s2k5_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st);  // the stem's layer 2
-        if (t != 0) return t < 0 ? t : 0;
-        t = isg_tap_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st);
-        if (t != 0) return t < 0 ? t : 0;
+    // the candidates, first taker runs:
+    if (!(g->KH == 1 && g->KW == 1)) {
+        ISG_TRY(isg_thin_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st));       // thin 3x3
+        ISG_TRY(isg_down_conv_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st));  // convT weights
+        ISG_TRY(isg_s2k5_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st));       // the stem's layer 2
+        ISG_TRY(isg_tap_wgrad(g, dy, x, dw, dbias, rep_stride, nrep, st));        // narrow spatial
     }
-    {
-        const int32_t t = pwg_try(g, dy, x, dw, dbias, rep_stride, nrep, st);
-        if (t != 0) return t < 0 ? t : 0;
-    }
+    ISG_TRY(pwg_try(g, dy, x, dw, dbias, rep_stride, nrep, st));  // 1x1 (pwk opt-in, then pwg)
+    // else the halo-staged MFMA kernel below
     WgArgs a{};
     a.dy = *dy; a.x = *x; a.dw = dw; a.dbias = dbias;
     a.rep_stride = rep_stride; a.nrep = nrep;
@@ -1098,23 +1038,13 @@ int32_t isg_dense_conv_wgrad(const isg_conv_geom* g, const isg_vtensor* dy, cons
     // halo floats (>= 768: the k-split / VALU partial sums reuse that space)
     const size_t xs = std::max<size_t>((size_t)max_nci(bnt) * a.hsp, 768);
     const size_t lds = ((size_t)a.BMT * 16 * kAStride + xs) * sizeof(float);
-#define WG_LAUNCH(T) hipLaunchKernelGGL((wgrad_kernel<T>), grid, dim3(kThreads), lds, st, a)
-    switch (tpw) {
-        case 1: WG_LAUNCH(1); break;
-        case 2: WG_LAUNCH(2); break;
-        case 3: WG_LAUNCH(3); break;
-        case 4: WG_LAUNCH(4); break;
-        case 5: case 6: WG_LAUNCH(6); break;
-        default: WG_LAUNCH(8); break;
-    }
-#undef WG_LAUNCH
+    with_tpw(tpw, [&](auto T) { hipLaunchKernelGGL((wgrad_kernel<decltype(T)::value>), grid, dim3(kThreads), lds, st, a); });
     return isg_check_launch("wgrad_kernel");
 }
 
-// ---- executor hooks (api.cpp): the 1x1 weight gradients of a side-stream batch, grouped --
-// isg_pwg_plan: > 0 (the instantiation key) when isg_conv_wgrad_rep would run this op on
-// pwg_kernel, the plan written into `plan` (isg_pwg_plan_bytes() bytes); 0 otherwise.
-// isg_pwg_run: launch n <= isg_pwg_group_max() plans of one key as one launch.
+// ---- executor hooks (api.cpp, contracts in launch.h): the 1x1 weight gradients of a
+// side-stream batch, grouped. isg_pwg_plan walks isg_conv_wgrad_rep's route to pwg_kernel:
+// that function's and isg_dense_conv_wgrad's refusals, then pwg_try's own two calls.
 extern "C" int32_t isg_pwg_plan_bytes() { return (int32_t)sizeof(PwgPlan); }
 extern "C" int32_t isg_pwg_group_max() { return kPwgGroup; }
 
@@ -1127,7 +1057,7 @@ extern "C" int32_t isg_pwg_plan(const isg_conv_geom* g, const isg_vtensor* dy, c
     if (g->w_ci && g->w_ci != g->Ci) return 0;
     if (vt_channels(dy) != g->Co || vt_channels(x) != g->Ci) return 0;
     PwgPlan& pl = *static_cast<PwgPlan*>(plan);
-    if (!pwg_plan(g, dy, x, dw, dbias, rep_stride, nrep, pl)) return 0;
+    if (!pwg_applies(g, dy, x) || !pwg_plan(g, dy, x, dw, dbias, rep_stride, nrep, pl)) return 0;
     return pl.key();
 }
 

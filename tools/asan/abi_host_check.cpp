@@ -5,7 +5,9 @@
 // (-Xarch_host -fsanitize=address, host half only): no device code, no GPU needed. It drives the
 // paths whose memory handling is host code — argument validation, the error plumbing,
 // the executor's record parsing and pointer fix-ups, the chunking of host item arrays —
-// with valid and malformed inputs; kernel launches fail cleanly without a device.
+// with valid and malformed inputs; kernel launches fail cleanly without a device. The
+// launchers' host predicates (csrc/launch.h, stage.h's fast ones) are driven directly on
+// host structs.
 // Exit 0 and no ASan report = pass.
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "../../include/isg.h"
+#include "../../instancesegmentation_amd/csrc/stage.h"  // launch.h's predicates + the fast ones
 
 static int failures = 0;
 #define EXPECT(c)                                                        \
@@ -37,7 +40,153 @@ static void put_op(std::vector<char>& b, int kind, const void* desc, int bytes,
     }
 }
 
+// csrc/launch.h: the predicates that pick a kernel and its template flags, on host structs
+static void check_launch_predicates() {
+    alignas(16) static float buf[64];
+    float* const ok = buf;
+    float* const off4 = buf + 1;  // 4 bytes off a 16-B boundary
+    EXPECT(aligned16(ok) && aligned16(nullptr) && !aligned16(off4));
+
+    isg_vtensor v{};
+    v.nseg = 2;
+    v.s[0].p = ok; v.s[0].n_stride = 64; v.s[0].C = 4;
+    v.s[1].p = ok + 4; v.s[1].n_stride = 128; v.s[1].C = 3;
+    EXPECT(vt_rows16(v) && vt_channels(&v) == 7);
+    { isg_vtensor t = v; t.s[1].p = off4; EXPECT(!vt_rows16(t)); }
+    { isg_vtensor t = v; t.s[0].n_stride = 65; EXPECT(!vt_rows16(t)); }  // n_stride % 4 == 1
+    {   // a BN_BWD y misaligned while p is aligned; y's stride; a NULL y has nothing to check
+        isg_vtensor t = v;
+        t.s[0].xform = ISG_XF_BN_BWD; t.s[0].y = off4; t.s[0].y_n_stride = 64;
+        EXPECT(!vt_rows16(t));
+        t.s[0].y = ok; t.s[0].y_n_stride = 66;
+        EXPECT(!vt_rows16(t));
+        t.s[0].y_n_stride = 64;
+        EXPECT(vt_rows16(t));
+        t.s[0].y = nullptr; t.s[0].y_n_stride = 1;
+        EXPECT(vt_rows16(t));
+        t.s[0].xform = ISG_XF_PLAIN; t.s[0].y = off4;  // a PLAIN segment's y is not an operand
+        EXPECT(vt_rows16(t));
+    }
+    {   // the residual forms: a BN_FWD y and a mat
+        isg_vtensor t = v;
+        t.s[1].xform = ISG_XF_BN_FWD; t.s[1].y = off4; t.s[1].y_n_stride = 64;
+        EXPECT(!vt_rows16(t) && isg_vt_res(&t));
+        t.s[1].y = ok;
+        EXPECT(vt_rows16(t));
+        t.mat = off4; t.mat_n_stride = 64;
+        EXPECT(!vt_rows16(t));
+        t.mat = ok; t.mat_n_stride = 6;
+        EXPECT(!vt_rows16(t));
+        t.mat_n_stride = 8;
+        EXPECT(vt_rows16(t));
+    }
+    {   // BN_BWD without y resolves to p at p's stride
+        isg_vtensor t = v;
+        t.s[0].xform = ISG_XF_BN_BWD;
+        const isg_vtensor r = isg_resolve_y(&t);
+        EXPECT(r.s[0].y == ok && r.s[0].y_n_stride == 64 && r.s[1].y == nullptr);
+        EXPECT(vt_rows16(r) == vt_rows16(t));
+    }
+
+    isg_sinks k{};
+    k.nsink = 2;
+    k.s[0].mode = ISG_SINK_STORE; k.s[0].p = ok; k.s[0].n_stride = 64;
+    k.s[1].mode = ISG_SINK_NONE; k.s[1].p = (float*)(uintptr_t)0x1235; k.s[1].n_stride = 7;  // ignored
+    EXPECT(sinks_rows16(k) && !sinks_read_operand(k) && !sinks_stat_on(k));
+    { isg_sinks t = k; t.s[0].p = off4; EXPECT(!sinks_rows16(t)); }
+    { isg_sinks t = k; t.s[0].n_stride = 61; EXPECT(!sinks_rows16(t)); }
+    { isg_sinks t = k; t.s[0].mode = ISG_SINK_ACCUM; EXPECT(sinks_rows16(t) && sinks_read_operand(t)); }
+    {   // an ACTBWD sink with y misaligned
+        isg_sinks t = k;
+        t.s[1].mode = ISG_SINK_ACTBWD; t.s[1].p = ok; t.s[1].n_stride = 64;
+        t.s[1].y = off4; t.s[1].y_n_stride = 64;
+        EXPECT(!sinks_rows16(t) && sinks_read_operand(t));
+        t.s[1].y = ok; t.s[1].y_n_stride = 62;
+        EXPECT(!sinks_rows16(t));
+        t.s[1].y_n_stride = 64;
+        EXPECT(sinks_rows16(t));
+    }
+
+    // stat_on: coef set, only stats, neither; fast: coef or training mode
+    static double stats[16];
+    {
+        isg_vtensor t = v;
+        t.s[1].xform = ISG_XF_BN_FWD;
+        EXPECT(!vt_stat_on(t) && !vt_fast(t));  // neither, eval mode (train == 0): the slow path
+        t.s[1].bn.train = 1;
+        EXPECT(!vt_stat_on(t) && vt_fast(t));
+        t.s[1].bn.stats = stats;
+        EXPECT(vt_stat_on(t) && vt_fast(t));
+        t.s[1].bn.train = 0;
+        EXPECT(vt_stat_on(t) && !vt_fast(t));
+        t.s[1].bn.coef = ok;
+        EXPECT(!vt_stat_on(t) && vt_fast(t));
+        t.s[1].xform = ISG_XF_PLAIN;  // no BatchNorm: its bn record is not read
+        t.s[1].bn.coef = nullptr;
+        EXPECT(!vt_stat_on(t) && vt_fast(t));
+        t.nseg = 1;
+        t.s[1].xform = ISG_XF_BN_BWD;  // past nseg
+        EXPECT(vt_fast(t) && !vt_stat_on(t));
+    }
+    {
+        isg_sinks t = k;
+        t.s[0].mode = ISG_SINK_ACTBWD; t.s[0].y = ok;
+        EXPECT(!sinks_stat_on(t) && !sinks_fast(t));
+        t.s[0].bn.stats = stats;
+        EXPECT(sinks_stat_on(t) && !sinks_fast(t));
+        t.s[0].bn.train = 1;
+        EXPECT(sinks_stat_on(t) && sinks_fast(t));
+        t.s[0].bn.coef = ok; t.s[0].bn.train = 0;
+        EXPECT(!sinks_stat_on(t) && sinks_fast(t));
+        t.s[0].mode = ISG_SINK_STORE; t.s[0].bn.coef = nullptr;
+        EXPECT(!sinks_stat_on(t) && sinks_fast(t));
+    }
+
+    const int want[9] = {1, 2, 3, 4, 6, 6, 8, 8, 8};
+    for (int t = 1; t <= 9; ++t)
+        EXPECT(with_tpw(t, [](auto T) { return (int)decltype(T)::value; }) == want[t - 1]);
+
+    // the geometry predicates: one true case, then each field flipped in turn
+    isg_conv_geom p{};
+    p.N = 2; p.Ci = 8; p.Co = 8; p.H = p.OH = 6; p.W = p.OW = 10; p.KH = p.KW = 1; p.SH = p.SW = 1;
+    p.DH = p.DW = 1; p.groups = 1;
+    EXPECT(geom_1x1_s1(&p));
+    for (int32_t isg_conv_geom::*f : {&isg_conv_geom::KH, &isg_conv_geom::KW, &isg_conv_geom::SH,
+                                      &isg_conv_geom::SW, &isg_conv_geom::PH, &isg_conv_geom::PW}) {
+        isg_conv_geom q = p;
+        q.*f += 1;
+        EXPECT(!geom_1x1_s1(&q));
+    }
+    isg_conv_geom d{};
+    d.N = 1; d.Ci = 3; d.Co = 16; d.H = 12; d.W = 16; d.OH = 6; d.OW = 8; d.KH = d.KW = 5;
+    d.SH = d.SW = 2; d.PH = d.PW = 2; d.DH = d.DW = 1; d.groups = 1; d.w_ci = 20;
+    EXPECT(geom_s2k5(&d));
+    for (int32_t isg_conv_geom::*f : {&isg_conv_geom::KH, &isg_conv_geom::KW, &isg_conv_geom::SH,
+                                      &isg_conv_geom::SW, &isg_conv_geom::PH, &isg_conv_geom::PW,
+                                      &isg_conv_geom::DH, &isg_conv_geom::DW, &isg_conv_geom::H,
+                                      &isg_conv_geom::W, &isg_conv_geom::OH, &isg_conv_geom::OW,
+                                      &isg_conv_geom::groups}) {
+        isg_conv_geom q = d;
+        q.*f += 1;
+        EXPECT(!geom_s2k5(&q));
+    }
+
+    int64_t rs = 100;
+    int32_t nr = 1;
+    norm_replicas(rs, nr);
+    EXPECT(rs == 0 && nr == 1);
+    rs = 100; nr = 0;
+    norm_replicas(rs, nr);
+    EXPECT(rs == 0 && nr == 1);
+    rs = 100; nr = 4;
+    norm_replicas(rs, nr);
+    EXPECT(rs == 100 && nr == 4);
+    EXPECT(launched(0) == 1 && launched(ISG_ERR_HIP) == ISG_ERR_HIP);
+    EXPECT(isg_cu_count() >= 1 && isg_cu_count() == isg_cu_count());  // 256 without a device
+}
+
 int main() {
+    check_launch_predicates();
     EXPECT(isg_abi_version() > 0);
     EXPECT(isg_stat_replicas() == ISG_STAT_REP);
     for (int i = 0; i <= 16; ++i) EXPECT(isg_record_size(i) > 0);

@@ -18,10 +18,12 @@ for s in "$ROOT"/instancesegmentation_amd/csrc/*.hip "$ROOT"/instancesegmentatio
          "$HERE/abi_host_check.cpp"; do
   o="$OUT/$(basename "${s%.*}").o"
   objs+=("$o")
-  if [ -f "$o" ] && [ "$o" -nt "$s" ] && [ "$o" -nt "$ROOT/instancesegmentation_amd/csrc/common.h" ] \
-     && [ "$o" -nt "$ROOT/instancesegmentation_amd/csrc/stage.h" ] \
-     && [ "$o" -nt "$ROOT/instancesegmentation_amd/csrc/crop_core.h" ] && [ "$o" -nt "$ROOT/include/isg.h" ]; then
-    continue
+  stale=0
+  if [ -f "$o" ]; then  # stale against its source and every header
+    for d in "$s" "$ROOT"/instancesegmentation_amd/csrc/*.h "$ROOT/include/isg.h"; do
+      [ "$o" -nt "$d" ] || stale=1
+    done
+    [ $stale = 1 ] || continue
   fi
   lang=""; case "$s" in *.cpp) lang="-x hip";; esac
   $HIPCC $FLAGS $lang -c "$s" -o "$o" &
