@@ -451,6 +451,32 @@ int32_t isg_mask_rle(const uint8_t* masks, int32_t K, int32_t H, int32_t W, cons
                      const int32_t* nsel, int32_t max_sel, uint32_t* runs, int64_t runs_cap,
                      int64_t* offsets /* [max_sel+1] */, void* work, isg_stream_t stream);
 
+/* COCO run-length decoding onto canvases (csrc/mask_rle_decode.hip; the contract is stated on
+ * the CPU by instancesegmentation_amd/rle.py `decode_canvas`): the inverse of isg_mask_rle,
+ * whose runs / offsets plug in unchanged. Slot j < n decodes the counts
+ * runs[offsets[j] .. offsets[j+1]) into masks[j] (row-major [H,W], every byte written, 0 or
+ * 255) and totals[j] = their unclipped sum; the caller compares totals with H*W, nothing is
+ * raised on the device. With ends = cumsum(counts), column-major position p = x*H + y
+ * belongs to run i = #{ends <= p} (zero-length runs are stepped over) and is 255 when i is
+ * odd and i < the number of counts: positions at or past the sum are background, runs past
+ * H*W are ignored. A slot whose range is empty or reversed, starts below 0 or reaches past
+ * runs_cap is the all-zero canvas with total 0; runs at index >= runs_cap are never read.
+ * Slots may overlap or repeat. offsets: device memory. masks: any byte address (dword stores
+ * where W % 4 == 0 and masks is 4-B aligned, byte stores otherwise).
+ * Refused with ISG_ERR_INVALID before any HIP call: n < 0, H <= 0, W <= 0, H*W >= 2^31,
+ * runs_cap < 0, a NULL pointer that would be used (runs and work may be NULL when
+ * runs_cap == 0), offsets / totals / work not 8-B aligned, runs not 4-B aligned.
+ * runs_cap >= 2^31 is ISG_ERR_UNSUPPORTED. n == 0 does nothing.
+ * Capturable: the launch geometry depends on (n, H, W, runs_cap) only, nothing is allocated
+ * or synchronised, and the result does not depend on what masks, totals or work held.
+ * work: isg_mask_rle_decode_workspace(n,H,W,runs_cap) bytes (-1 for sizes the call
+ * refuses), caller-owned. */
+int64_t isg_mask_rle_decode_workspace(int32_t n, int32_t H, int32_t W, int64_t runs_cap);
+int32_t isg_mask_rle_decode(const uint32_t* runs, int64_t runs_cap,
+                            const int64_t* offsets /* [n+1], device */, int32_t n,
+                            int32_t H, int32_t W, uint8_t* masks /* [n,H,W] */,
+                            int64_t* totals /* [n] */, void* work, isg_stream_t stream);
+
 /* ---- scoring (csrc/mask_eval.hip) ------------------------ */
 
 /* Crop-space validation IoU counts (the contract is stated on the CPU by

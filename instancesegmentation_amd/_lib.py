@@ -241,6 +241,9 @@ SIGNATURES = {
     "isg_mask_rle_workspace": (c_int64, [c_int32, c_int32, c_int32]),
     "isg_mask_rle": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
                                c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "isg_mask_rle_decode_workspace": (c_int64, [c_int32, c_int32, c_int32, c_int64]),
+    "isg_mask_rle_decode": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "isg_mask_iou_crops": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p,
                                      c_void_p]),
     "isg_mask_iou_matrix_workspace": (c_int64, [c_int32, c_int32, c_int32, c_int32]),

@@ -7,12 +7,23 @@ The counting runs on the GPU (csrc/mask_eval.hip); this module holds
   * their wrappers `crop_iou_counts` (device tensors in, a device table out, no sync) and
     `MaskMatcher` (owns workspace and outputs, one device-to-host copy per call);
   * `mean_iou_from_counts`, train_loop.tensors_mean_iou from the integer counts;
-  * `MaskAP`, a numpy accumulator of mask average precision on top of the IoU matrix.
+  * `MaskAP`, a numpy accumulator of mask average precision on top of the IoU matrix;
+  * `RleDecoder`, COCO RLE counts back onto device canvases (csrc/mask_rle_decode.hip; its
+    CPU statement is rle.decode_canvas), and on top of it the offline scorer of an existing
+    results file:
+
+        python -m instancesegmentation_amd.evaluate --results OUT/results.json -i IMAGES
+            [--mask-root DIR] [-o eval.json]
+
+    It walks the images as `infer` does, decodes each image's detections on the GPU,
+    matches them against the sidecar `instance_mask` ground truth and writes what
+    `infer --evaluate` would have written for a complete run (default: eval.json next to
+    the results file).
 
 Foreground is `>= 128` everywhere: on a crop that is tensor2mask (p * 255 truncated to
 uint8, train_instance.py:398-399) followed by the build's mask_iou threshold, on a canvas
-it is the mask-NMS contract's threshold. torch and libisg.so are imported by the two
-wrappers only: everything else here is numpy.
+it is the mask-NMS contract's threshold. torch and libisg.so are imported by the wrappers
+and the scorer only: everything else here is numpy.
 """
 import numpy as np
 
@@ -261,3 +272,207 @@ class MaskAP:
         out["AP75"] = ap[5]
         out["AR"] = float(np.mean(ar))
         return out
+
+
+# ---- COCO RLE back onto canvases --------------------------------------------------------
+def _counts_u32(counts):
+    """One mask's counts as a contiguous uint32 array (ValueError outside [0, 2^32))."""
+    c = np.asarray(counts).reshape(-1)
+    if not c.size:
+        return np.zeros(0, np.uint32)
+    if c.dtype.kind not in "iu" or c.min() < 0 or c.max() >= 2 ** 32:
+        raise ValueError("counts must be integers in [0, 2^32)")
+    return np.ascontiguousarray(c.astype(np.uint32))
+
+
+class RleDecoder:
+    """isg_mask_rle_decode for images of one size: owns the runs, offsets, totals, workspace
+    and canvas buffers for up to max_masks masks of max_counts counts together (rle.py
+    `decode_canvas` is the CPU statement)."""
+
+    def __init__(self, image_hw, max_masks, max_counts, device=None):
+        import torch
+
+        from . import _lib as L
+        self.device = torch.device(device or "cuda")
+        if self.device.type != "cuda":
+            raise RuntimeError("RleDecoder runs on the MI355X only (rle.decode_canvas is the CPU "
+                               "statement)")
+        self.H, self.W = int(image_hw[0]), int(image_hw[1])
+        self.max_masks, self.max_counts = int(max_masks), int(max_counts)
+        ws = L.lib().isg_mask_rle_decode_workspace(self.max_masks, self.H, self.W, self.max_counts)
+        if ws < 0:
+            raise ValueError(f"RleDecoder: bad sizes {image_hw} {max_masks} {max_counts}")
+        dev = self.device
+        self.runs = torch.empty(max(self.max_counts, 1), dtype=torch.int32, device=dev)  # uint32 bits
+        self.offsets = torch.empty(self.max_masks + 1, dtype=torch.int64, device=dev)
+        self.totals = torch.empty(max(self.max_masks, 1), dtype=torch.int64, device=dev)
+        self.work = torch.empty(ws // 8, dtype=torch.int64, device=dev)
+        self.masks = torch.empty((self.max_masks, self.H, self.W), dtype=torch.uint8, device=dev)
+
+    def decode(self, counts, strict=True):
+        """counts: a list of uint32 count arrays, one per mask -> the uint8 [n,H,W] device
+        view of their canvases (0 / 255; valid until the next call), ready for
+        MaskMatcher.iou. strict: a mask whose counts do not sum to H*W raises ValueError;
+        strict=False returns (canvases, totals int64 [n]) and leaves the judgement to the
+        caller (the canvas of such a mask is rle.decode_canvas's)."""
+        import torch
+
+        from . import _lib as L
+        per = [_counts_u32(c) for c in counts]
+        n = len(per)
+        if n > self.max_masks:
+            raise ValueError(f"{n} masks > capacity {self.max_masks}")
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(c) for c in per])
+        total = int(off[-1])
+        if total > self.max_counts:
+            raise ValueError(f"{total} counts > capacity {self.max_counts}")
+        if n == 0:
+            empty = np.zeros(0, np.int64)
+            return self.masks[:0] if strict else (self.masks[:0], empty)
+        if total:
+            self.runs[:total].copy_(torch.from_numpy(np.concatenate(per).view(np.int32)))
+        self.offsets[:n + 1].copy_(torch.from_numpy(off))
+        L.check(L.lib().isg_mask_rle_decode(self.runs.data_ptr(), total, self.offsets.data_ptr(), n,
+                                            self.H, self.W, self.masks.data_ptr(),
+                                            self.totals.data_ptr(), self.work.data_ptr(),
+                                            L.stream_ptr(self.device)), "mask_rle_decode")
+        totals = self.totals[:n].cpu().numpy()  # the one copy back (it synchronises)
+        if not strict:
+            return self.masks[:n], totals
+        for j in np.flatnonzero(totals != self.H * self.W):
+            raise ValueError(f"mask {int(j)}: counts sum to {int(totals[j])}, not H*W = "
+                             f"{self.H * self.W}")
+        return self.masks[:n]
+
+
+# ---- scoring an existing results.json ---------------------------------------------------
+def group_detections(results, image_paths):
+    """The COCO results list grouped by image: {path: [result, ...]} with every path of
+    `image_paths` present (images without detections score their ground truth) and the
+    detections of an image in file order. File names map to ids through rle.image_id_of.
+    Raises ValueError for two images with one id and for an id that matches no image."""
+    import os
+
+    from .rle import image_id_of
+    by_id, groups = {}, {}
+    for path in image_paths:
+        image_id = image_id_of(os.path.splitext(os.path.basename(path))[0])
+        if image_id in by_id:
+            raise ValueError(f"{by_id[image_id]} and {path} both map to image_id {image_id!r}")
+        by_id[image_id] = path
+        groups[path] = []
+    for k, r in enumerate(results):
+        image_id = r["image_id"]
+        # JSON keeps 42 and "42" apart; so does image_id_of (digits are always the int)
+        if isinstance(image_id, bool) or image_id not in by_id:
+            raise ValueError(f"result {k}: image_id {image_id!r} matches no image")
+        groups[by_id[image_id]].append(r)
+    return groups
+
+
+def segmentation_counts(seg, H, W):
+    """uint32 counts of one result's `segmentation` for an H x W image: a COCO RLE whose
+    counts are the compressed string (rle.from_string) or the uncompressed list. Raises
+    ValueError for a polygon list and for a `size` that is not the image's."""
+    from .rle import from_string
+    if not isinstance(seg, dict) or "counts" not in seg or "size" not in seg:
+        raise ValueError("segmentation must be a COCO RLE {\"size\", \"counts\"}; polygons are "
+                         "not supported")
+    if [int(v) for v in seg["size"]] != [H, W]:
+        raise ValueError(f"segmentation size {seg['size']} is not the image's {[H, W]}")
+    c = seg["counts"]
+    return from_string(c) if isinstance(c, (str, bytes)) else _counts_u32(c)
+
+
+DECODE_MASKS = 16  # masks one decode / match round holds (the matcher's max_det)
+
+
+def score_results(results_path, image_dir, mask_root=None, device=None):
+    """Score a COCO results file against the sidecar ground truth of `image_dir`, as
+    `infer --evaluate` scores a run: returns the eval.json dictionary."""
+    import json
+    import os
+
+    import torch
+    from PIL import Image
+
+    from .infer import RLE_CAPACITY_FACTOR, list_images, load_ground_truth
+    dev = torch.device(device or "cuda")
+    with open(results_path) as f:
+        results = json.load(f)
+    if not isinstance(results, list):
+        raise ValueError(f"{results_path}: a COCO results file is a list")
+    paths = list_images(image_dir)
+    groups = group_detections(results, paths)
+    mask_root = mask_root or image_dir
+    ap, images, decoders, matchers = MaskAP(), [], {}, {}
+    for path in paths:
+        with Image.open(path) as im:
+            W, H = im.size
+        dets = groups[path]
+        counts = [segmentation_counts(r["segmentation"], H, W) for r in dets]
+        gt, gt_index = load_ground_truth(os.path.splitext(path)[0] + ".json", mask_root, H, W)
+        matcher = matchers.get((H, W))
+        if matcher is None or matcher.max_gt < len(gt):
+            matcher = matchers[(H, W)] = MaskMatcher((H, W), DECODE_MASKS, max(len(gt), 1), dev)
+        gt_dev = torch.from_numpy(gt).to(dev)
+        need = max([len(c) for c in counts], default=0)
+        dec = decoders.get((H, W))
+        if dec is None or dec.max_counts < need:
+            dec = decoders[(H, W)] = RleDecoder(
+                (H, W), DECODE_MASKS, max(RLE_CAPACITY_FACTOR * DECODE_MASKS * (H + W), need), dev)
+        rows, k = [], 0
+        while k < len(counts):  # a chunk: up to DECODE_MASKS masks that fit the runs buffer
+            e, used = k, 0
+            while (e < len(counts) and e - k < dec.max_masks
+                   and (e == k or used + len(counts[e]) <= dec.max_counts)):
+                used += len(counts[e])
+                e += 1
+            canvases, totals = dec.decode(counts[k:e], strict=False)
+            for j in np.flatnonzero(totals != H * W):
+                raise ValueError(f"{os.path.basename(path)}, detection {k + int(j)}: counts sum to "
+                                 f"{int(totals[j])}, not H*W = {H * W}")
+            rows.append(matcher.iou(canvases, gt_dev)[0])
+            k = e
+        iou = np.concatenate(rows) if rows else np.zeros((0, len(gt)))
+        m = ap.add_image([float(r["score"]) for r in dets], iou)
+        images.append({"image": os.path.basename(path), "detections": len(dets),
+                       "matched_gt@0.5": [gt_index[j] if j >= 0 else -1
+                                          for j in m["matched_gt@0.5"]],
+                       "iou@0.5": m["iou@0.5"]})
+    return {"summary": ap.summary(), "results": results_path, "images": images}
+
+
+def parse_args(argv=None):
+    import argparse
+    parser = argparse.ArgumentParser(
+        prog="python -m instancesegmentation_amd.evaluate",
+        description="score an existing COCO results.json (mask AP) against the sidecar "
+                    "instance_mask ground truth")
+    parser.add_argument("--results", required=True, help="results.json of infer --format coco")
+    parser.add_argument("-i", "--test-image-dir", required=True, help="image test dir")
+    parser.add_argument("--mask-root", default=None,
+                        help="directory the instance_mask paths are relative to (default: the "
+                             "image directory)")
+    parser.add_argument("-o", "--output", default=None,
+                        help="where eval.json goes (default: next to the results file)")
+    return parser.parse_args(argv)
+
+
+def main(argv=None):
+    import json
+    import os
+    args = parse_args(argv)
+    out = score_results(args.results, args.test_image_dir, args.mask_root)
+    path = args.output or os.path.join(os.path.dirname(os.path.abspath(args.results)), "eval.json")
+    with open(path, "w") as f:
+        json.dump(out, f)
+    print("eval: " + " ".join(f"{k} {v:.4f}" if isinstance(v, float) else f"{k} {v}"
+                              for k, v in out["summary"].items()))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

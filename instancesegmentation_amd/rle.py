@@ -1,7 +1,8 @@
 """COCO run-length encoding of binary masks (numpy only: no torch, no GPU).
 
-This module is the CPU statement of the contract that csrc/mask_rle.hip implements, and
-the codec between the kernel's `counts` and the strings COCO tools read.
+This module is the CPU statement of the contracts that csrc/mask_rle.hip (`encode`) and
+csrc/mask_rle_decode.hip (`decode_canvas`) implement, and the codec between the kernels'
+`counts` and the strings COCO tools read.
 
 Binarisation: a pixel is set when mask >= 128 (the threshold of the mask-NMS).
 Counts: the binarised H x W mask flattened column-major (pixel (x, y) at position
@@ -40,6 +41,23 @@ def decode(counts, H, W):
         raise ValueError(f"counts sum to {int(c.sum())}, not H*W = {H * W}")
     vals = (np.arange(len(c)) & 1).astype(bool)
     return np.repeat(vals, c).reshape(W, H).T.copy()
+
+
+def decode_canvas(counts, H, W):
+    """(uint8 [H,W] canvas of 0 / 255, total) of `counts`: the CPU statement of the contract
+    csrc/mask_rle_decode.hip implements. Total, where `decode` is strict: with ends =
+    cumsum(counts), position p = x*H + y belongs to run i = the number of ends <= p (so
+    zero-length runs are stepped over) and is 255 when i is odd and i < len(counts).
+    Positions at or past the sum are background, runs past H*W are ignored; `total` is the
+    unclipped sum (the mask is well-formed when total == H*W). Empty counts: all zero, 0."""
+    c = np.asarray(counts).reshape(-1)
+    if c.size and (c.dtype.kind not in "iu" or c.min() < 0 or c.max() >= 2 ** 32):
+        raise ValueError("counts must be integers in [0, 2^32)")
+    ends = np.cumsum(c.astype(np.int64))
+    i = np.searchsorted(ends, np.arange(H * W, dtype=np.int64), side="right")
+    bits = ((i & 1) == 1) & (i < len(c))
+    canvas = np.ascontiguousarray(bits.reshape(W, H).T).astype(np.uint8) * np.uint8(255)
+    return canvas, int(ends[-1]) if len(c) else 0
 
 
 def to_string(counts):

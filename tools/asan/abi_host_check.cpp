@@ -220,6 +220,42 @@ int main() {
         EXPECT(isg_mask_rle(px, 1, 4, 4, nullptr, nullptr, 1, nullptr, 0, nullptr, wk, nullptr) ==
                ISG_ERR_INVALID);  // NULL offsets
     }
+    EXPECT(isg_mask_rle_decode_workspace(16, 1024, 1024, 2049) == 8 * (2050 + 2));
+    EXPECT(isg_mask_rle_decode_workspace(1, 65536, 32768, 16) == -1);
+    EXPECT(isg_mask_rle_decode_workspace(1, 4, 4, -1) == -1);
+    {   // isg_mask_rle_decode rejects these before any HIP call
+        uint32_t rn[8] = {};
+        int64_t off[4] = {}, tot[4] = {};
+        uint64_t wk[16] = {};
+        uint8_t px[64] = {};
+        EXPECT(isg_mask_rle_decode(rn, 8, off, 0, 4, 4, nullptr, nullptr, nullptr, nullptr) ==
+               ISG_OK);  // n == 0
+        EXPECT(isg_mask_rle_decode(rn, 8, off, -1, 4, 4, px, tot, wk, nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_mask_rle_decode(rn, 8, off, 1, 0, 4, px, tot, wk, nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_mask_rle_decode(rn, 8, off, 1, 4, -4, px, tot, wk, nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_mask_rle_decode(rn, -1, off, 1, 4, 4, px, tot, wk, nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_mask_rle_decode(rn, 8, off, 1, 65536, 32768, px, tot, wk, nullptr) ==
+               ISG_ERR_INVALID);  // H*W == 2^31
+        EXPECT(std::strstr(isg_last_error(), "2^31") != nullptr);
+        EXPECT(isg_mask_rle_decode(nullptr, 8, off, 1, 4, 4, px, tot, wk, nullptr) ==
+               ISG_ERR_INVALID);  // runs == NULL with runs_cap > 0
+        EXPECT(isg_mask_rle_decode(rn, 8, nullptr, 1, 4, 4, px, tot, wk, nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_mask_rle_decode(rn, 8, off, 1, 4, 4, nullptr, tot, wk, nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_mask_rle_decode(rn, 8, off, 1, 4, 4, px, nullptr, wk, nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_mask_rle_decode(rn, 8, off, 1, 4, 4, px, tot, nullptr, nullptr) == ISG_ERR_INVALID);
+        EXPECT(std::strstr(isg_last_error(), "NULL") != nullptr);
+        EXPECT(isg_mask_rle_decode((const uint32_t*)((const char*)rn + 2), 4, off, 1, 4, 4, px, tot,
+                                   wk, nullptr) == ISG_ERR_INVALID);  // runs not 4-B aligned
+        EXPECT(isg_mask_rle_decode(rn, 8, (const int64_t*)((const char*)off + 4), 1, 4, 4, px, tot,
+                                   wk, nullptr) == ISG_ERR_INVALID);  // offsets not 8-B aligned
+        EXPECT(isg_mask_rle_decode(rn, 8, off, 1, 4, 4, px, (int64_t*)((char*)tot + 4), wk,
+                                   nullptr) == ISG_ERR_INVALID);
+        EXPECT(isg_mask_rle_decode(rn, 8, off, 1, 4, 4, px, tot, (char*)wk + 4, nullptr) ==
+               ISG_ERR_INVALID);
+        EXPECT(std::strstr(isg_last_error(), "alignment") != nullptr);
+        EXPECT(isg_mask_rle_decode(rn, (int64_t)1 << 31, off, 1, 4, 4, px, tot, wk, nullptr) ==
+               ISG_ERR_UNSUPPORTED);
+    }
 
     EXPECT(isg_train_crop_workspace(8) == 8 * 2048 && isg_train_crop_workspace(0) == 0);
     {   // isg_train_crop rejects these before any HIP call (the descriptors are host memory)

@@ -12,7 +12,13 @@ csrc/mask_eval.hip), at the sizes the project runs:
         (ii) detections x ground truth at K = G = 16, 1024 x 1024 (the bench's inference
              configuration): iou_matrix_cpu on the host against MaskMatcher.iou from device
              canvases (kernels + the one copy), wall clock; isg_mask_iou_matrix alone by
-             device events.
+             device events;
+        (iii) COCO RLE back onto canvases, n = 16 masks of 1024 x 1024 (the detections of
+             (ii), run-length encoded): rle.decode per mask, stacked and uploaded, against
+             RleDecoder.decode (packing, upload, kernels, the totals' copy back), wall clock;
+             isg_mask_rle_decode alone by device events, with its share of the HBM rate for
+             the canvas bytes it writes; and, on its own, rle.from_string over the same
+             masks' strings (the parse stays on the host).
     Rounds alternate the legs; every leg is warmed up first; the two answers of each pair
     are compared before anything is timed. Prints one JSON line. Needs the GPU: there is
     no fallback.
@@ -161,6 +167,52 @@ def main(argv=None):
     mat["speedup_host_over_device"] = round(mat["host_ms"]["median"] / mat["device_ms"]["median"], 2)
     mat["read_bytes"] = (K + G) * H * W
     out["iou_matrix_k16_g16_1024"] = mat
+
+    # (iii) COCO RLE back onto canvases: the detections of (ii), run-length encoded
+    from instancesegmentation_amd import rle as R
+    counts = [R.encode(m) for m in det_h]
+    strings = [R.to_string(c) for c in counts]
+    total = sum(len(c) for c in counts)
+    decoder = E.RleDecoder((H, W), K, total, dev)
+
+    def host_decode():
+        stack = np.stack([R.decode(c, H, W) for c in counts]).astype(np.uint8) * np.uint8(255)
+        return torch.from_numpy(stack).to(dev)
+
+    def device_decode():
+        return decoder.decode(counts)
+
+    def parse_strings():
+        return [R.from_string(s) for s in strings]
+
+    assert torch.equal(host_decode(), device_decode()) and torch.equal(device_decode(), det_d)
+    assert all(np.array_equal(a, b) for a, b in zip(parse_strings(), counts))
+
+    def decode_kernels():  # on what device_decode() uploaded
+        L.check(L.lib().isg_mask_rle_decode(decoder.runs.data_ptr(), total,
+                                            decoder.offsets.data_ptr(), K, H, W,
+                                            decoder.masks.data_ptr(), decoder.totals.data_ptr(),
+                                            decoder.work.data_ptr(), L.stream_ptr(dev)))
+
+    times = {"host_ms": [], "device_ms": [], "from_string_ms": []}
+    wall_ms(host_decode, 1)
+    wall_ms(device_decode, 3)
+    event_ms(decode_kernels, 2)
+    ktime = []
+    for _ in range(args.rounds):
+        times["host_ms"].append(wall_ms(host_decode, 1))
+        times["device_ms"].append(wall_ms(device_decode, args.reps))
+        times["from_string_ms"].append(wall_ms(parse_strings, 1))
+        ktime.append(event_ms(decode_kernels, args.reps))
+    dec = {k: stats(v) for k, v in times.items()}
+    dec["kernels_ms"] = stats(ktime)
+    dec["speedup_host_over_device"] = round(dec["host_ms"]["median"] / dec["device_ms"]["median"], 2)
+    dec["counts"] = total
+    dec["string_bytes"] = sum(len(s) for s in strings)
+    dec["written_bytes"] = K * H * W
+    dec["kernels_share_of_measured_hbm"] = round(
+        K * H * W / (dec["kernels_ms"]["median"] * 1e-3) / HBM_MEASURED, 4)
+    out["rle_decode_n16_1024"] = dec
     print(json.dumps(out))
     return 0
 
