@@ -138,7 +138,10 @@ typedef struct {
     int64_t y_n_stride;
     const float* slope;    /* ACTBWD + PRELU */
     double* slope_grad;    /* ACTBWD + PRELU, C doubles per replica */
-    isg_bn bn;             /* ACTBWD; bn.stats==NULL means "no BN" (identity) */
+    isg_bn bn;             /* ACTBWD; bn.stats==NULL means "no BN" (identity). bn.C must equal C
+                              (the sink covers its whole layer): the kernels lay gsum / gxsum
+                              out by the sink's C. Only a vseg may read the first channels of
+                              a wider layer (its bn.C > C) */
     const float* r;        /* ACTBWD residual form: the tail's residual term, or NULL */
     int64_t r_n_stride;
     const float* old;      /* ACTBWD residual form: gradient already accumulated for v, or NULL */
@@ -748,6 +751,10 @@ int32_t isg_exec_ms2(const void* ops, int32_t nops, void* const* table, isg_stre
 int32_t isg_record_size(int32_t which);
 
 const char* isg_last_error(void);
+/* The kernel name given to this thread's latest launch check (e.g. "tap_conv_kernel"; an error
+ * return before the launch appends ": dynamic LDS"), "" before any: a static string, for tests
+ * that assert which kernel a dispatch chain chose. Costs one thread-local pointer store. */
+const char* isg_last_launch(void);
 int32_t isg_abi_version(void);
 /* ISG_STAT_REP the library was built with (accumulator replica count). */
 int32_t isg_stat_replicas(void);

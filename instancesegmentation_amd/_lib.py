@@ -271,6 +271,7 @@ SIGNATURES = {
     "isg_exec_ms": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
     "isg_exec_ms2": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "isg_last_error": (c_char_p, []),
+    "isg_last_launch": (c_char_p, []),
     "isg_abi_version": (c_int32, []),
     "isg_stat_replicas": (c_int32, []),
     "isg_record_size": (c_int32, [c_int32]),

@@ -25,7 +25,11 @@ int32_t isg_set_error(int32_t code, const char* fmt, ...) {
     return code;
 }
 
+// the name of the thread's latest launch (isg_last_launch): every `what` is a string literal
+static thread_local const char* g_last_launch = "";
+
 int32_t isg_check_launch(const char* what) {
+    g_last_launch = what;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return isg_set_error(ISG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     return ISG_OK;
@@ -79,6 +83,7 @@ static bool partial_w(const isg_conv_geom* g) { return g->w_ci > 0 && g->w_ci !=
 extern "C" {
 
 const char* isg_last_error(void) { return g_last_error.c_str(); }
+const char* isg_last_launch(void) { return g_last_launch; }
 int32_t isg_abi_version(void) { return 14; }  // 14: isg_train_crop_aug (train_crop.hip)
 int32_t isg_stat_replicas(void) { return ISG_STAT_REP; }
 

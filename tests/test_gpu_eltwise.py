@@ -7,6 +7,8 @@ proved on the CPU by tests/test_eltwise_cases_cpu.py).
 
 Every output buffer starts as NaN (a canary for integer / double buffers); a kernel that
 writes a slice must leave every byte around it as it was."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -14,67 +16,16 @@ import torch
 from instancesegmentation_amd import _lib as L
 from oracle import epilogue_oracle as E
 from tests import eltwise_cases as EC
-from tests.isg_helpers import (bn_spec_eval, bn_spec_train, call, ptr, rep_fold, rep_zeros, sinks,
-                               stream, struct, vt)
+from tests import isg_helpers
+from tests.isg_helpers import (NAN, POISON, bits, bn_spec_eval, bn_spec_train, call, dev, ptr,  # noqa: F401
+                               rep_fold, rep_spread, rep_zeros, same_bits, sinks, stream, struct, vt)
 from tests.test_gpu_kernels import close
 from tests.test_gpu_step_epilogue import report
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 N = EC.N
-NAN = float("nan")
-POISON = 1e30  # around the slice of an input: a misplaced read shows
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).to(DEV)  # a copy: the cases are read-only
-
-
-def bits(t):
-    """The raw words of a float tensor as numpy (NaN compares as its bits)."""
-    t = t.detach().contiguous().cpu()
-    return t.view(torch.int64 if t.dtype == torch.float64 else torch.int32).numpy()
-
-
-def same_bits(got, want, what):
-    bad = int((bits(got) != bits(want)).sum())
-    assert bad == 0, f"{what}: {bad} elements differ bitwise"
-
-
-class Slab:
-    """A [N, C, H, W] channel slice at channel c0 of a wider [N, C + pad, H, W] buffer, which
-    starts `off` floats into its allocation. `data` fills the slice, `fill` everything else."""
-
-    def __init__(self, C, H, W, data=None, fill=NAN, pad=3, c0=2, off=0):
-        self.C, self.c0 = C, c0
-        self.flat = torch.full((off + N * (C + pad) * H * W,), fill, dtype=torch.float32, device=DEV)
-        self.buf = self.flat[off:].view(N, C + pad, H, W)
-        if data is not None:
-            self.buf[:, c0:c0 + C] = dev(np.asarray(data, np.float32))
-        self.n_stride = (C + pad) * H * W
-        self.ptr = self.buf[0, c0].data_ptr()
-        self.before = self.flat.clone()
-
-    def get(self):
-        return self.buf[:, self.c0:self.c0 + self.C]
-
-    def outside_untouched(self, what, whole=False):
-        changed = torch.from_numpy(bits(self.flat) != bits(self.before))
-        if not whole:
-            inside = torch.zeros_like(self.buf, dtype=torch.bool)
-            inside[:, self.c0:self.c0 + self.C] = True
-            off = self.flat.numel() - inside.numel()
-            changed[off:] &= ~inside.reshape(-1).cpu()
-        assert not changed.any(), f"{what}: {int(changed.sum())} words around the slice changed"
-
-
-def rep_spread(vals):
-    """A replicated accumulator whose replicas sum to `vals` (dyadic shares: to within an fp64
-    rounding), so a consumer that read replica 0 alone would be off by half."""
-    vals = np.asarray(vals, np.float64)
-    w = [2.0 ** -(r + 1) for r in range(L.STAT_REP - 1)]
-    w.append(1.0 - sum(w))
-    return dev(np.concatenate([wi * vals for wi in w]))
+Slab = functools.partial(isg_helpers.Slab, N=N)
 
 
 def seg_spec(sg, slab, keep, H, W):

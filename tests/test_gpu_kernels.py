@@ -69,7 +69,8 @@ DENSE = [
     (4, 4, 5, 7, 1, 1, 0, 1),
     (16, 48, 24, 20, 1, 1, 0, 1),
     (4, 32, 16, 12, 1, 1, 0, 1),
-    # tap_conv coverage: Ci % 4 != 0, 3 row tiles, ragged edges, multi-tile grids
+    # tap_conv coverage: Ci % 4 != 0, 3 row tiles, ragged edges, multi-tile grids (the k8 s4
+    # shape is not tap_conv's: halo_conv forward, the implicit GEMM's input gradient)
     (3, 16, 64, 48, 5, 2, 2, 1),
     (16, 36, 33, 45, 3, 1, 1, 1),
     (20, 16, 130, 100, 5, 2, 2, 1),
@@ -94,9 +95,9 @@ DENSE = [
     (8, 12, 40, 24, 5, 2, 2, 1),
     # ... on the LDS-staged form (cell columns % 4 == 0): two column blocks, ragged rows
     (16, 16, 74, 136, 5, 2, 2, 1),
-    # 5x5 s2 with <= 16 channels (the stem's second conv; tap_conv by default, the
-    # opt-in s2k5_fwd in test_s2k5_fwd): partial column block, odd output rows, fewer
-    # channels than the 16-lane fragments
+    # 5x5 s2 with <= 16 channels (the stem's second conv: s2k5_fwd where W % 4 == 0 and the
+    # rows are 16-B aligned, else tap_conv; test_gpu_conv_forms.py asserts which): partial
+    # column block, odd output rows, fewer channels than the 16-lane fragments
     (16, 16, 134, 200, 5, 2, 2, 1),
     (12, 8, 40, 36, 5, 2, 2, 1),
     # thin 3x3 (thin_conv / thin_wgrad, 4 pixels per lane): ragged row count, 1 -> 4
