@@ -674,7 +674,19 @@ int32_t isg_kp_pool(const isg_kp_stem* a, isg_stream_t stream);
  *        parameter gradients, added into replica (workgroup % nrep) of each (replica r at
  *        + r*rep_stride elements; NULL skips one); `ring` as written by the forward
  *        (required). Replaces the unfused isg_convT_fwd + isg_conv_fwd (+ their dgrad /
- *        wgrad) pair, which round-trips the intermediate through HBM. */
+ *        wgrad) pair, which round-trips the intermediate through HBM.
+ * Refused before any launch. ISG_ERR_INVALID: NULL w1 / w2, N, Hi or Wi < 1, NULL out (fwd),
+ * NULL dout or ring (bwd), nrep < 1, or nrep > 1 without a rep_stride. ISG_ERR_UNSUPPORTED: a
+ * residual input or sink form, nseg outside 1..ISG_MAX_SEGS, a segment with C <= 0, segments
+ * that do not add up to 16 channels, x.N / x.H / x.W other than N / Hi / Wi, N*16*Hi*Wi >=
+ * 2^31; in the backward also nsink outside 0..ISG_MAX_SEGS (0: no input gradient), with
+ * nsink > 0 sinks that do not cover [0, 16) in order (s[0].c0 = 0, s[i].c0 = s[i-1].c0 +
+ * s[i-1].C, the last ending at 16; sinks need not split where the segments do), an ACTBWD
+ * sink, a STORE / ACCUM sink with statistics or without a buffer, and a sink with `bias` (the
+ * kernel would not apply it).
+ * isg_last_launch after the backward names the instantiation: "head_bwd_kernel<vec>" (16-B
+ * staging and dx stores: Wi % 4 == 0 and dout, every segment's p and every written sink's p
+ * 16-B aligned with image strides that are multiples of 4) or "head_bwd_kernel<scalar>". */
 #define ISG_HEAD_RING(Hi, Wi) (2 * (4 * (int64_t)(Wi) + 2) + 2 * 4 * (int64_t)(Hi))
 typedef struct {
     isg_vtensor x;               /* [N,16,Hi,Wi] */

@@ -746,21 +746,36 @@ int32_t check_head(const isg_mask_head* a, bool bwd) {
         return isg_set_error(ISG_ERR_INVALID, "mask head: NULL weights or bad size");
     if (isg_vt_res(&a->x) || (bwd && isg_sinks_res(&a->dx)))
         return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head: residual form");
+    if (a->x.nseg < 1 || a->x.nseg > ISG_MAX_SEGS)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head: 1..%d input segments", ISG_MAX_SEGS);
     int C = 0;
-    for (int s = 0; s < a->x.nseg; ++s) C += a->x.s[s].C;
-    if (a->x.nseg < 1 || a->x.nseg > ISG_MAX_SEGS || C != kCi || a->x.H != a->Hi || a->x.W != a->Wi)
-        return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head: input must be %d channels of %dx%d",
-                             kCi, a->Hi, a->Wi);
+    for (int s = 0; s < a->x.nseg; ++s) {
+        if (a->x.s[s].C <= 0)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head: input segment %d has no channels", s);
+        C += a->x.s[s].C;
+    }
+    if (C != kCi || a->x.N != a->N || a->x.H != a->Hi || a->x.W != a->Wi)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head: input must be %d x %d channels of %dx%d",
+                             a->N, kCi, a->Hi, a->Wi);
     if ((int64_t)a->N * 16 * a->Hi * a->Wi >= ((int64_t)1 << 31))
         return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head: output exceeds 32-bit offsets");
     if (!bwd) return a->out ? ISG_OK : isg_set_error(ISG_ERR_INVALID, "mask head: NULL output");
     if (!a->dout) return isg_set_error(ISG_ERR_INVALID, "mask head bwd: NULL dlogits");
+    if (a->dx.nsink < 0 || a->dx.nsink > ISG_MAX_SEGS)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head bwd: 0..%d sinks", ISG_MAX_SEGS);
+    int c = 0;  // the kernel resolves a sink per input channel (sink_row): all 16, in order
     for (int s = 0; s < a->dx.nsink; ++s) {
         const isg_sink& k = a->dx.s[s];
+        if (k.c0 != c || k.C <= 0)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head bwd: sinks must cover [0, %d) in order", kCi);
+        c += k.C;
         if (k.mode == ISG_SINK_ACTBWD || (k.mode != ISG_SINK_NONE && (k.stats || !k.p)))
             return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head bwd: input-gradient sinks must be "
                                  "STORE / ACCUM without statistics");
+        if (k.bias) return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head bwd: a sink bias is not applied");
     }
+    if (a->dx.nsink > 0 && c != kCi)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "mask head bwd: sinks cover %d of %d channels", c, kCi);
     if (a->nrep < 1 || (a->nrep > 1 && a->rep_stride <= 0))
         return isg_set_error(ISG_ERR_INVALID, "mask head bwd: bad replicas");
     if (!a->ring)
@@ -838,9 +853,10 @@ extern "C" int32_t isg_mask_head_bwd(const isg_mask_head* a, isg_stream_t st) {
     const int ntx = (OW + TX - 1) / TX, nty = (OH + TY - 1) / TY;
     const int ntiles = ntx * nty * a->N;
     const int grid = head_bwd_blocks(a->N, a->Hi, a->Wi);
-    if (head_bwd_vec(a))
+    if (head_bwd_vec(a)) {
         hipLaunchKernelGGL(head_bwd_kernel<true>, dim3(grid), dim3(2 * kThreads), 0, st, *a, ntx, nty, ntiles);
-    else
-        hipLaunchKernelGGL(head_bwd_kernel<false>, dim3(grid), dim3(2 * kThreads), 0, st, *a, ntx, nty, ntiles);
-    return isg_check_launch("head_bwd_kernel");
+        return isg_check_launch("head_bwd_kernel<vec>");
+    }
+    hipLaunchKernelGGL(head_bwd_kernel<false>, dim3(grid), dim3(2 * kThreads), 0, st, *a, ntx, nty, ntiles);
+    return isg_check_launch("head_bwd_kernel<scalar>");
 }
