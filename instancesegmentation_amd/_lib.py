@@ -116,7 +116,7 @@ def head_ring_floats(Hi, Wi):
     return 4 * (2 * (4 * Wi + 2) + 2 * 4 * Hi)
 
 
-# executor records (api.cpp)
+# executor records (csrc/exec.cpp)
 class ConvRec(Structure):
     _fields_ = [("g", Geom), ("a", VTensor), ("w", c_void_p), ("out", Sinks)]
 

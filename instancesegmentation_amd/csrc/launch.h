@@ -1,6 +1,6 @@
 // Host side of the conv launchers, stated once: the internal launchers' prototypes, the
 // operand and geometry predicates that pick a kernel and its template flags, and the launch
-// idioms. Included by api.cpp and (through common.h) by every .hip file, the defining ones
+// idioms. Included by api.cpp, exec.cpp and (through common.h) by every .hip file, the defining ones
 // too, so a signature that drifts from its callers' fails to compile or link.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,9 +10,30 @@
 
 #include "../../include/isg.h"
 
-// ---- error plumbing (api.cpp) --------------------------------------------------------
+// ---- error plumbing (error.cpp) ------------------------------------------------------
 int32_t isg_set_error(int32_t code, const char* fmt, ...);
 int32_t isg_check_launch(const char* what);  // ISG_OK / error
+
+// ---- conv geometry: consistent, dense or depthwise (every public conv entry of api.cpp,
+// the executor's grouping): ISG_OK / error ----------------------------------------------------
+inline int32_t check_geom(const isg_conv_geom* g) {
+    if (!g) return isg_set_error(ISG_ERR_INVALID, "conv: NULL geometry");
+    if (g->N < 1 || g->Ci < 1 || g->Co < 1 || g->H < 1 || g->W < 1 || g->KH < 1 || g->KW < 1 ||
+        g->SH < 1 || g->SW < 1 || g->DH < 1 || g->DW < 1 || g->PH < 0 || g->PW < 0)
+        return isg_set_error(ISG_ERR_INVALID, "conv: invalid geometry");
+    const int oh = (g->H + 2 * g->PH - g->DH * (g->KH - 1) - 1) / g->SH + 1;
+    const int ow = (g->W + 2 * g->PW - g->DW * (g->KW - 1) - 1) / g->SW + 1;
+    if (oh != g->OH || ow != g->OW)
+        return isg_set_error(ISG_ERR_INVALID, "conv: output %dx%d but geometry gives %dx%d", g->OH,
+                             g->OW, oh, ow);
+    if (g->groups != 1 && !(g->groups == g->Ci && g->Ci == g->Co))
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "conv: groups=%d (dense or depthwise only)",
+                             g->groups);
+    if (g->w_ci < 0 || (g->w_ci > 0 && (g->w_ci < g->Ci || g->groups != 1)))
+        return isg_set_error(ISG_ERR_INVALID, "conv: weight input channels %d < Ci %d", g->w_ci,
+                             g->Ci);
+    return ISG_OK;
+}
 
 // ---- internal launchers ----------------------------------------------------------------
 // "tries": 1 launched, 0 not for this kernel (the caller goes on to the next), < 0 error

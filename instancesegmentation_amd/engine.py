@@ -87,7 +87,7 @@ def _fill(obj, spec, base, fix):
 
 
 class Record:
-    OPF_SIDE, OPF_JOIN, OPF_FORK_NOW = 1, 2, 4  # executor header flags (api.cpp)
+    OPF_SIDE, OPF_JOIN, OPF_FORK_NOW = 1, 2, 4  # executor header flags (csrc/exec.cpp)
     # a join's count of the most recent side records it does NOT wait for (_join_exclusions)
     EXCL_SHIFT, EXCL_MAX = 8, (1 << 20) - 1
 
@@ -676,7 +676,7 @@ def _join_exclusions(recs):
     otherwise cover the side stream's whole tail, e.g. bottle1_1's 2x2 conv waiting for its
     own forked residual branch (pool + convm) when it only reads the stem's pools. The
     count of excluded (later) side records goes into the header flags' upper bits
-    (api.cpp OPF_JOIN); joins without recorded dependencies wait for everything."""
+    (csrc/exec.cpp ISG_OPF_JOIN, SideSched::join_upto); joins without recorded dependencies wait for everything."""
     order = []
     for r in recs:
         if r.flags & Record.OPF_JOIN:
@@ -1728,7 +1728,7 @@ class Plan:
             for r in recs:
                 if side or r.kind == L.OP_GRAD_FINAL:
                     # the finalisation lists are independent of each other: forked behind
-                    # the fold, dealt over both side streams (api.cpp), joined at the end
+                    # the fold, dealt over both side streams (csrc/exec.cpp), joined at the end
                     # of the list (5 launches of ~5 us each ran back to back on the main
                     # stream at the very end of the step)
                     r.flags |= Record.OPF_SIDE | Record.OPF_FORK_NOW

@@ -255,7 +255,7 @@ def test_loaded_adam_hyperparameters_reach_the_captured_step():
 
 
 def test_side_close_orders_after_second_side_stream(monkeypatch):
-    """ADVICE r03 (api.cpp flush): with two gradient buckets and bucket 1's replica fold +
+    """ADVICE r03 (the executor's flush, csrc/exec.cpp): with two gradient buckets and bucket 1's replica fold +
     gradient finalisation on the side stream (ISG_SIDE_CLOSE=1), that fold must run after
     the weight gradients dealt onto the second side stream (ISG_SIDE2=1). The gradients must
     equal those of the same plan with one side stream (the default) and of the default plan,

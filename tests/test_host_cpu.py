@@ -217,7 +217,8 @@ def test_keypoint_stem_plan_and_synthetic_keypoints():
 
 def _joined_before(recs, k):
     """The side-stream records (list indices) the main stream has waited for by the time
-    record k runs, by the executor's rule (api.cpp isg_exec_ms2): a join with exclusion
+    record k runs, by the executor's rule (csrc/exec.cpp isg_exec_ms2; test_host_asan.py checks this mirror
+    against the executor itself): a join with exclusion
     count e (header flags >> Record.EXCL_SHIFT, 0 < e <= side records so far) waits for all
     but the e most recent side records; any other join waits for every one."""
     from instancesegmentation_amd.engine import Record

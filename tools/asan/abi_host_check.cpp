@@ -7,7 +7,8 @@
 // the executor's record parsing and pointer fix-ups, the chunking of host item arrays —
 // with valid and malformed inputs; kernel launches fail cleanly without a device. The
 // launchers' host predicates (csrc/launch.h, stage.h's fast ones) are driven directly on
-// host structs.
+// host structs. The executor cases here cover record parsing only: which stream and which
+// event every record gets is checked by exec_order_check.cpp, next to this file.
 // Exit 0 and no ASan report = pass.
 #include <cstdio>
 #include <cstdlib>

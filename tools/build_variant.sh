@@ -16,7 +16,10 @@ for s in $SRC/*.hip; do
   objs="$objs $OUT/$f.o"
   while [ $(jobs -r | wc -l) -ge 6 ]; do sleep 1; done
 done
-/opt/rocm/bin/hipcc $FL -x hip -c $SRC/api.cpp -o $OUT/api.o
+for f in api error exec; do
+  /opt/rocm/bin/hipcc $FL -x hip -c $SRC/$f.cpp -o $OUT/$f.o
+  objs="$objs $OUT/$f.o"
+done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o instancesegmentation_amd/libisg_$NAME.so $objs $OUT/api.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o instancesegmentation_amd/libisg_$NAME.so $objs
 echo built instancesegmentation_amd/libisg_$NAME.so

@@ -21,8 +21,11 @@ for s in $SRC/*.hip; do
   /opt/rocm/bin/hipcc $FL -c $s -o $OUT/$f.o &
   objs="$objs $OUT/$f.o"
 done
-/opt/rocm/bin/hipcc $FL -x hip -c $SRC/api.cpp -o $OUT/api.o &
+for f in api error exec; do
+  /opt/rocm/bin/hipcc $FL -x hip -c $SRC/$f.cpp -o $OUT/$f.o &
+  objs="$objs $OUT/$f.o"
+done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/libisg_stamp.so $objs $OUT/api.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT/libisg_stamp.so $objs
 /opt/rocm/bin/hipcc -O2 -std=c++17 kbench.cpp -o $OUT/kbench -ldl -L$OUT -lisg_stamp -Wl,-rpath,'$ORIGIN'
 echo built $OUT/kbench
