@@ -127,7 +127,7 @@ struct OpHdr {
 };
 enum { ISG_OPF_SIDE = 1, ISG_OPF_JOIN = 2, ISG_OPF_FORK_NOW = 4 };  // FORK_NOW: forked at the next main-stream op
 // flags >> 8 of a JOIN: how many of the most recent side records (in list order) the op does
-// NOT depend on — it waits only for the side work up to the one before them (engine.py
+// NOT depend on — it waits only for the side work up to the one before them (engine/schedule.py
 // _join_exclusions); 0 = wait for all side work
 constexpr int kJoinExclShift = 8;
 

@@ -5,7 +5,7 @@ Same classes, constructor signatures, attribute names, parameter order and
 state_dict keys (588 entries for Segment(20)), so reference checkpoints and
 `optim.Adam(model.parameters())` (train_instance.py:297) keep working. What changes
 is `forward`: each module's structure is described once in `emit` and executed by
-the MI355X engine (instancesegmentation_amd/engine.py -> libisg.so HIP kernels),
+the MI355X engine (instancesegmentation_amd/engine/ -> libisg.so HIP kernels),
 not by torch eager kernels. There is no CPU path: a CPU tensor raises.
 
 Reference anchors: Conv :34-48, init_head_s4 :19-31, Bottleneck3x3 :52-79,

@@ -297,14 +297,18 @@ def test_bn_final_launches_match_default(monkeypatch):
     the default plan (coefficients evaluated by the consumers). Three replays each. (The
     fused form, finalised by the producer's last workgroup, failed this check in round 4 —
     1.4e-3 of scale, deterministic — and was removed in round 5.)"""
-    from instancesegmentation_amd import engine
+    from instancesegmentation_amd import _lib as L
+    from instancesegmentation_amd.engine import knobs
     fx = SegmentFixture("segment20_n2_128.npz")
     xs, y = _inputs(fx.x), torch.from_numpy(fx.mask).to(DEV)
 
     def grads(final):
-        monkeypatch.setattr(engine, "_BN_FINAL", final)
+        monkeypatch.setattr(knobs, "BN_FINAL", final)
         tr = Trainer(_model(fx), fx.n, [(fx.n, 3, fx.h, fx.w), (fx.n, 17, fx.h, fx.w)],
                      device=DEV).capture()
+        # the patch reached the plan: finalisation launches in both passes, or in neither
+        for ol in (tr.plan.fwd, tr.plan.bwd):
+            assert any(r.kind == L.OP_BN_FINAL for r in ol.recs) == final
         sd = tr.optimizer_state_dict()
         sd["param_groups"][0]["lr"] = 0.0
         tr.load_optimizer_state_dict(sd)

@@ -361,11 +361,10 @@ def test_forward_fork_group_captured_behind_the_next_main_record(monkeypatch):
     so that conv does not wait on the side queue's tail; every side record still precedes
     its join, and a group is never moved past a record that joins it. =0 keeps the capture
     order, =2 delays every group."""
-    from instancesegmentation_amd import engine as E
-    from instancesegmentation_amd.engine import Record
+    from instancesegmentation_amd.engine import Record, knobs
 
     def plan(mode):
-        monkeypatch.setattr(E, "_FORK_DELAY", mode)
+        monkeypatch.setattr(knobs, "FORK_DELAY", mode)
         return Plan(Segment(20), [(2, 3, 128, 128), (2, 17, 3)], True, True, (False, False))
 
     def check(recs):
@@ -377,6 +376,7 @@ def test_forward_fork_group_captured_behind_the_next_main_record(monkeypatch):
     p0, p1, p2 = plan("0"), plan("1"), plan("2")
     lab = lambda p: [r.label for r in p.fwd.recs]
     assert sorted(lab(p0)) == sorted(lab(p1)) == sorted(lab(p2))
+    assert len({tuple(lab(p)) for p in (p0, p1, p2)}) == 3  # the patch reached _delay_forks
     side0 = [r.label for r in p0.fwd.recs if r.flags & Record.OPF_SIDE]
     first = lab(p1).index("init_conv.layer1")
     assert lab(p0).index("init_conv.layer1") > lab(p0).index(side0[0])
