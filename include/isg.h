@@ -637,7 +637,25 @@ int32_t isg_train_crop_aug(const uint8_t* arena, int64_t arena_bytes, const isg_
  *          sum^2 of every changed pixel
  *   wgrad: dw[co][c_kp0+j][tap] += sum_p dy[co][p] * map_j(tap(p)), dy a vtensor
  *   pool : out[n][c0+j] = max_pool(map_j, k) (k x k windows, stride k)
- * geom: the conv (Ci = the weight's input channels, Co <= 16, groups 1). */
+ * geom: the conv (Ci = the weight's input channels, Co <= 16, groups 1).
+ * A keypoint with visible <= 0, or a NaN or infinite coordinate, draws nothing; finite
+ * coordinates of any size are safe (a window wholly outside the image is empty).
+ * Refused before any launch, nothing written. With r = sqrt(-log(threshold)) * sigma:
+ *   all three, ISG_ERR_INVALID: a NULL descriptor or kp, nparts outside 1..32, sigma <= 0 or
+ *     NaN, threshold outside (0, 1) or NaN, g.N, g.H or g.W < 1;
+ *   all three, ISG_ERR_UNSUPPORTED: r > 120;
+ *   fwd and wgrad, ISG_ERR_UNSUPPORTED: groups != 1, Co outside 1..16, KH*KW > 49, a stride
+ *     or dilation < 1, c_kp0 < 0, c_kp0 + nparts != Ci, or a 16 x 16 output tile's footprint
+ *     S*15 + D*(K-1) + 1 above 64 on either axis;
+ *   fwd: NULL w or y (ISG_ERR_INVALID); 16 * nparts * KH*KW > 8192 (ISG_ERR_UNSUPPORTED);
+ *   wgrad, in this order: a residual-form dy (ISG_ERR_UNSUPPORTED); NULL dw, dy.nseg != 1 or
+ *     dy.s[0].C != Co (ISG_ERR_INVALID); nrep < 1, or nrep > 1 with rep_stride <= 0
+ *     (ISG_ERR_INVALID); Co * KH*KW > 512 (ISG_ERR_UNSUPPORTED); a widest window, int(2r) + 2
+ *     pixels, that reaches more than 256 output columns, (int(2r) + 1 + DW*(KW-1))/SW + 1, or
+ *     whose staged footprint exceeds 4096 floats at any column count nc up to that:
+ *     ((nr-1)*SH + DH*(KH-1) + 1) * ((nc-1)*SW + DW*(KW-1) + 1) with nr = min(max(1, 256/nc),
+ *     ceil(nrow/4)), nrow the row count alike (ISG_ERR_UNSUPPORTED);
+ *   pool: NULL out, k < 1, or k not dividing g.H and g.W (ISG_ERR_INVALID). */
 typedef struct {
     const double* kp;            /* [N][nparts][3] */
     int32_t nparts, c_kp0;

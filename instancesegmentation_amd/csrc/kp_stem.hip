@@ -380,14 +380,27 @@ int32_t isg_kp_stem_wgrad(const isg_kp_stem* s, isg_stream_t st) {
         return isg_set_error(ISG_ERR_INVALID, "kp_stem_wgrad: bad replicas");
     if (a.Co * a.KK > 2 * kThreads)
         return isg_set_error(ISG_ERR_UNSUPPORTED, "kp_stem_wgrad: %d x %d taps", a.Co, a.KK);
-    // the widest window reaches (2r+2)/SW + KW output columns; its footprint must fit
+    // The kernel's staging must fit for every window. A window is at most wmax = int(2r) + 2
+    // pixels wide (floor(kx+r+1) - floor(kx-r) <= floor(2r+1) + 1; clipping only narrows it),
+    // and a window [x0, x1) reaches the output columns ceil((x0+PW-DW(KW-1))/SW) ..
+    // floor((x1-1+PW)/SW): ncol <= (wd - 1 + DW*(KW-1))/SW + 1, the dilated tap span included
+    // (an earlier bound, wmax/SW + KW + 1, left it out and accepted dilated geometries whose
+    // chunks overran dyl / hl). Rows alike, and a block's band is ceil(nrow/4) of them. A
+    // narrower (clipped) window stages more rows per chunk, nr = min(256/ncol, band), so the
+    // footprint fh*fw is checked at every column count the kernel can meet, not only the widest.
     const int wmax = (int)(2.0 * a.r) + 2;
-    const int ncol = wmax / a.SW + a.KW + 1;
-    const int rows_per = std::max(1, kMaxWgPix / ncol);
-    const int fw = (ncol - 1) * a.SW + a.DW * (a.KW - 1) + 1;
-    const int fh = (rows_per - 1) * a.SH + a.DH * (a.KH - 1) + 1;
-    if (ncol > kMaxWgPix || fw * fh > kMaxWgFoot)
-        return isg_set_error(ISG_ERR_UNSUPPORTED, "kp_stem_wgrad: window footprint %dx%d", fh, fw);
+    const int ncol = (wmax - 1 + a.DW * (a.KW - 1)) / a.SW + 1;
+    const int nrow = (wmax - 1 + a.DH * (a.KH - 1)) / a.SH + 1;
+    const int band = (nrow + 3) / 4;  // gridDim.y = 4 below
+    if (ncol > kMaxWgPix)
+        return isg_set_error(ISG_ERR_UNSUPPORTED, "kp_stem_wgrad: window of %d output columns", ncol);
+    for (int nc = 1; nc <= ncol; ++nc) {
+        const int nr = std::min(std::max(1, kMaxWgPix / nc), band);
+        const int fw = (nc - 1) * a.SW + a.DW * (a.KW - 1) + 1;
+        const int fh = (nr - 1) * a.SH + a.DH * (a.KH - 1) + 1;
+        if (fw * fh > kMaxWgFoot)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "kp_stem_wgrad: window footprint %dx%d", fh, fw);
+    }
     a.dy = s->dy; a.dw = s->dw;
     a.rep_stride = s->nrep > 1 ? s->rep_stride : 0;
     a.nrep = s->nrep;
