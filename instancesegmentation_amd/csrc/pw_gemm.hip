@@ -15,6 +15,8 @@
 // = 2 mod 32 banks, B rows = 16 mod 32). The epilogue routes each output row through its
 // sink (store + bias + BN statistics, accumulate, or activation backward with the
 // BN-backward sums), resolved once per workgroup into LDS.
+#include <cstring>
+
 #include "stage.h"
 
 namespace {
@@ -57,6 +59,119 @@ ISG_DEV float row16_sum(float v) {
     x = __builtin_bit_cast(int, v);
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, false));
     return v;
+}
+
+// ---- pieces the slab kernel (pwx) and the K-pipelined kernel (pwp) share ------------------
+// The pixel an accumulator column holds: column pl of pixel tile ct of the block at p0
+// (P < 2^31, host check). Columns past the problem read image 0, pixel 0 and store nothing.
+struct TilePx {
+    bool pv;
+    int n, pix;
+};
+ISG_DEV TilePx tile_px(int64_t p0, int ct, int pl, int64_t P, int HW) {
+    const int64_t pe = p0 + ct * 16 + pl;
+    TilePx e;
+    e.pv = pe < P;
+    e.n = e.pv ? (int)((uint32_t)pe / (uint32_t)HW) : 0;
+    e.pix = e.pv ? (int)pe - e.n * HW : 0;
+    return e;
+}
+
+// One branch-free MFMA pass over kn (a multiple of 16) channels staged in LDS. The A
+// fragment is read 4 k-steps at a time with one ds_read_b128: MFMA step j of k-group g
+// gives lane slot kk the channel g + 4kk + j, for A and B alike (a permutation of the
+// reduction order only). aoff / boff: the lane's offsets of tile i at g = 0.
+template <int TPW>
+ISG_DEV void pw_mfma_span(const float* As, const float* Xs, const int (&aoff)[TPW], const int (&boff)[TPW],
+                          int kn, int XS, f32x4 (&acc)[TPW]) {
+    for (int g = 0; g < kn; g += 16) {
+        f32x4 a4[TPW];
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) a4[i] = *reinterpret_cast<const f32x4*>(&As[aoff[i] + g]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < TPW; ++i) {
+                const float bv = Xs[boff[i] + (g + j) * XS];
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[i][j], bv, acc[i], 0, 0, 0);
+            }
+    }
+}
+
+// The generic (any number of sinks) epilogue, a tile at a time; the lane holds
+// D[row = rt*16 + kk*4 + r][pixel e]. Every row's record comes from LDS (ri).
+// Sink operands of the tile's rows (saved forward output for ACTBWD, old value for ACCUM);
+// other rows load a dummy word at `any`
+ISG_DEV void tile_sink_operands(const RowInfo* ri, int rt, int kk, const TilePx& e, const float* any,
+                                float (&pre)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const RowInfo& qi = ri[rt * 16 + kk * 4 + r];
+        const float* src = any;
+        int64_t off = 0;
+        if (qi.mode == ISG_SINK_ACTBWD) { src = qi.y; off = (int64_t)e.n * qi.yns + e.pix; }
+        if (qi.mode == ISG_SINK_ACCUM) { src = qi.p; off = (int64_t)e.n * qi.ns + e.pix; }
+        if (!e.pv) { src = any; off = 0; }
+        pre[r] = gld(src, off);
+    }
+}
+// The tile through its rows' sinks; s0 / s1 / s2: the values each sink reduces (stage.h
+// sink_row_apply's, with the operand already loaded)
+ISG_DEV void tile_to_sinks(const RowInfo* ri, int rt, int kk, const TilePx& e, const f32x4& acc,
+                           const float (&pre)[4], float (&s0)[4], float (&s1)[4], float (&s2)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        s0[r] = s1[r] = s2[r] = 0.f;
+        const RowInfo& qi = ri[rt * 16 + kk * 4 + r];
+        if (!e.pv || qi.mode < 0 || qi.mode == ISG_SINK_NONE) continue;
+        float v = acc[r];
+        const int64_t off = (int64_t)e.n * qi.ns + e.pix;
+        if (qi.mode == ISG_SINK_STORE) {
+            v += qi.bias;
+            gst(qi.p, off, v);
+            s0[r] = v;
+            s1[r] = v * v;
+        } else if (qi.mode == ISG_SINK_ACCUM) {
+            gst(qi.p, off, pre[r] + v);
+            s0[r] = v;
+            s1[r] = v * v;
+        } else {
+            const float y = pre[r];
+            const float z = (y - qi.f.mean) * qi.f.scale + qi.f.beta;
+            float gv = v;
+            if (qi.act == ISG_ACT_RELU) {
+                gv = z > 0.f ? v : 0.f;
+            } else if (qi.act == ISG_ACT_PRELU) {
+                gv = z > 0.f ? v : v * qi.f.slope;
+                s2[r] = z > 0.f ? 0.f : z * v;
+            }
+            gst(qi.p, off, gv);
+            s0[r] = gv;
+            s1[r] = gv * (y - qi.f.mean);
+        }
+    }
+}
+// The tile's 16-pixel sums into the wave's partials red[wave][slot][row] (zeroed before)
+ISG_DEV void tile_red(float (*red)[4][kMaxBM], int wave, int rt, int kk, int pl, int Mb, const float (&s0)[4],
+                      const float (&s1)[4], const float (&s2)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float t0 = row16_sum(s0[r]);
+        const float t1 = row16_sum(s1[r]);
+        const float t2 = row16_sum(s2[r]);
+        const int rl = rt * 16 + kk * 4 + r;
+        if (pl == 0 && rl < Mb) {
+            red[wave][0][rl] += t0;
+            red[wave][1][rl] += t1;
+            red[wave][2][rl] += t2;
+        }
+    }
+}
+// The waves' partials of row rl folded in a fixed order (deterministic statistics)
+ISG_DEV void red_fold(float (*red)[4][kMaxBM], int rl) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        red[0][j][rl] = ((red[0][j][rl] + red[1][j][rl]) + red[2][j][rl]) + red[3][j][rl];
 }
 
 // TPW: 16x16 accumulator tiles per wave = (BM/16 row tiles x 4 pixel tiles) / 4 waves
@@ -535,18 +650,7 @@ __global__ __launch_bounds__(kThreads) void pwx_kernel(PwxArgs a) {
     f32x4 acc[TPW];
 #pragma unroll
     for (int i = 0; i < TPW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int g = 0; g < Kp; g += 16) {
-        f32x4 a4[TPW];
-#pragma unroll
-        for (int i = 0; i < TPW; ++i) a4[i] = *reinterpret_cast<const f32x4*>(&As[aoff[i] + g]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int i = 0; i < TPW; ++i) {
-                const float bv = Xs[boff[i] + (g + j) * XS];
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[i][j], bv, acc[i], 0, 0, 0);
-            }
-    }
+    pw_mfma_span<TPW>(As, Xs, aoff, boff, Kp, XS, acc);
     STAMP(4);
     // ---- phase 5: epilogue; lane holds D[row = rt*16 + kk*4 + r][pixel = ct*16 + pl] ----
     // sink operands first (saved forward output for ACTBWD, old value for ACCUM), all in
@@ -555,21 +659,7 @@ __global__ __launch_bounds__(kThreads) void pwx_kernel(PwxArgs a) {
 #pragma unroll
         for (int i = 0; i < TPW; ++i) {
             const int t = min(wave + 4 * i, nt - 1);
-            const int rt = t / CT, ct = t % CT;
-            const int64_t pe = p0 + ct * 16 + pl;
-            const bool pve = pe < a.P;
-            const int ne = pve ? (int)((uint32_t)pe / (uint32_t)a.HW) : 0;
-            const int pixe = pve ? (int)pe - ne * a.HW : 0;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const RowInfo& qi = ri[rt * 16 + kk * 4 + r];
-                const float* src = w;
-                int64_t off = 0;
-                if (qi.mode == ISG_SINK_ACTBWD) { src = qi.y; off = (int64_t)ne * qi.yns + pixe; }
-                if (qi.mode == ISG_SINK_ACCUM) { src = qi.p; off = (int64_t)ne * qi.ns + pixe; }
-                if (!pve) { src = w; off = 0; }
-                pre[i][r] = gld(src, off);
-            }
+            tile_sink_operands(ri, t / CT, kk, tile_px(p0, t % CT, pl, a.P, a.HW), w, pre[i]);
         }
     }
     const bool need_red = sinks_need_red(a.out);
@@ -680,83 +770,16 @@ __global__ __launch_bounds__(kThreads) void pwx_kernel(PwxArgs a) {
         if (t >= nt) continue;  // wave-uniform
         const int rt = t / CT, ct = t % CT;
         if (rt * 16 >= Mb) continue;
-        const int64_t pe = p0 + ct * 16 + pl;
-        const bool pve = pe < a.P;
-        const int ne = pve ? (int)((uint32_t)pe / (uint32_t)a.HW) : 0;
-        const int pixe = pve ? (int)pe - ne * a.HW : 0;
-        float s0[4], s1[4], s2[4], s3[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            s0[r] = s1[r] = s2[r] = s3[r] = 0.f;
-            const int rl = rt * 16 + kk * 4 + r;
-            const RowInfo& qi = ri[rl];
-            if (!pve || qi.mode < 0 || qi.mode == ISG_SINK_NONE) continue;
-            float v = acc[i][r];
-            const int64_t off = (int64_t)ne * qi.ns + pixe;
-            if (qi.mode == ISG_SINK_STORE) {
-                v += qi.bias;
-                gst(qi.p, off, v);
-                s0[r] = v;
-                s1[r] = v * v;
-            } else if (qi.mode == ISG_SINK_ACCUM) {
-                gst(qi.p, off, pre[i][r] + v);
-                s0[r] = v;
-                s1[r] = v * v;
-            } else {
-                const float y = pre[i][r];
-                float z = (y - qi.f.mean) * qi.f.scale + qi.f.beta;
-                ChanCoef k2 = {0.f, 1.f, 0.f, 0.f};
-                if constexpr (RES) {  // residual form: + old gradient, + residual term
-                    v = pro[i][r] + v;
-                    float rv = prr[i][r];
-                    if (rbn_out) {  // the residual's own BatchNorm (two-BN tail)
-                        k2 = tabK2[rl];
-                        rv = (rv - k2.c0) * k2.c1 + k2.c2;
-                    }
-                    z = z + rv;
-                }
-                float gv = v;
-                if (qi.act == ISG_ACT_RELU) {
-                    gv = z > 0.f ? v : 0.f;
-                } else if (qi.act == ISG_ACT_PRELU) {
-                    gv = z > 0.f ? v : v * qi.f.slope;
-                    s2[r] = z > 0.f ? 0.f : z * v;
-                }
-                gst(qi.p, off, gv);
-                if constexpr (RES) {
-                    if (ks.s0.p2)
-                        gst(ks.s0.p2, (int64_t)(rl + m0 - ks.s0.c0) * a.HW + (int64_t)ne * ks.s0.p2ns + pixe,
-                            ks.s0.p2acc ? pp2[i][r] + gv : gv);
-                    if (rbn_out) s3[r] = gv * (prr[i][r] - k2.c0);  // centred on the residual's mean
-                }
-                s0[r] = gv;
-                s1[r] = gv * (y - qi.f.mean);
-            }
-        }
-        if (need_red) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float t0 = row16_sum(s0[r]);
-                const float t1 = row16_sum(s1[r]);
-                const float t2 = row16_sum(s2[r]);
-                const float t3 = rbn_out ? row16_sum(s3[r]) : 0.f;
-                const int rl = rt * 16 + kk * 4 + r;
-                if (pl == 0 && rl < Mb) {
-                    red[wave][0][rl] += t0;
-                    red[wave][1][rl] += t1;
-                    red[wave][2][rl] += t2;
-                    red[wave][3][rl] += t3;
-                }
-            }
-        }
+        // (the residual form has one sink: it never comes here)
+        float s0[4], s1[4], s2[4];
+        tile_to_sinks(ri, rt, kk, tile_px(p0, ct, pl, a.P, a.HW), acc[i], pre[i], s0, s1, s2);
+        if (need_red) tile_red(red, wave, rt, kk, pl, Mb, s0, s1, s2);
     }
     if (need_red) {
         __syncthreads();
         STAMP(6);
         for (int rl = tid; rl < Mb; rl += kThreads) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                red[0][j][rl] = ((red[0][j][rl] + red[1][j][rl]) + red[2][j][rl]) + red[3][j][rl];
+            red_fold(red, rl);
             if constexpr (SINK1) sink_row_flush1(a.out.s[0], m0 + rl, red[0][0][rl], red[0][1][rl], red[0][2][rl]);
             else sink_row_flush(a.out, m0 + rl, red[0][0][rl], red[0][1][rl], red[0][2][rl]);
             if (rbn_out && a.out.s[0].rbn.stats) {  // the residual BatchNorm's backward sums
@@ -769,6 +792,307 @@ __global__ __launch_bounds__(kThreads) void pwx_kernel(PwxArgs a) {
         }
     }
     STAMP(7);
+}
+
+// ---- pwp: K-pipelined kernel (aligned layers whose K has no whole-K slab) -----------------
+// Between the two kernels above: K goes in chunks of 64 channels through two LDS buffers,
+// with pwx's 16-B loads, branch-free transform and b128 A fragments, and chunk c+1's global
+// loads issued into registers before chunk c's MFMA pass and stored after it — one barrier
+// per chunk, the loads under the MFMAs. A workgroup owns BM = 16 * TPW <= 64 rows x 64
+// pixels; wave w owns pixel tile w of every row tile. K is reduced in ascending order (no
+// split-K; pwp_pos). One prologue round trip as in pwx phase 1 (coefficient and sink records), with
+// the first chunk's loads in it.
+// Bank layout: As row stride 72 = 8 mod 64 (pwx's, conflict-free b128 fragment reads). The
+// lanes of an MFMA step read Xs rows 4 apart (pw_mfma_span), so a 32-lane group of the b32
+// B reads is conflict-free when 4 * XS = 16 mod 32: XS = 68 (pwx's 80 puts kk and kk + 1 on
+// one bank, and at 68 two workgroups fit a CU: 79,360 B each).
+// Outside its envelope (residual forms, vtensor.mat, a residual BatchNorm): host refusal.
+constexpr int kPpKC = 64;
+constexpr int kPpAS = kPpKC + 8;
+constexpr int kPpXS = kBP + 4;
+constexpr int kPpMaxBM = 64;
+// workgroups a launch should reach before its row blocks stop halving (measured: DESIGN 3.4)
+#ifndef ISG_PWP_MINB
+#define ISG_PWP_MINB 384
+#endif
+constexpr int kPwpMinBlocks = ISG_PWP_MINB;
+constexpr int kPpOffRi = kMaxK * (int)sizeof(ChanCoef);
+constexpr int kPpOffA = kPpOffRi + kPpMaxBM * (int)sizeof(RowInfo);
+static_assert(kPpOffA % 16 == 0 && kMaxK <= kThreads && kPpMaxBM <= kThreads, "pwp tables: one entry per thread");
+static_assert(2 * kPpKC * kPpXS >= 4 * 4 * kMaxBM, "BN partials alias the activation buffers");
+constexpr int pwp_lds(int bm) { return kPpOffA + 2 * (bm * kPpAS + kPpKC * kPpXS) * (int)sizeof(float); }
+
+// a chunk's global loads, held in registers across the previous chunk's MFMA pass
+template <bool HY>
+struct PwpRegs {
+    f32x4 x[4], y[HY ? 4 : 1], w[4];
+};
+// what a lane keeps over the K loop: its pixel quad q of the block and channel row cr of a
+// 16-row staging pass (pwx phase 2's lane map), that quad's image and pixel
+struct PwpLane {
+    int tid, q, cr, n, pix, m0, Mb;
+    bool pv;
+};
+
+// 4x4 transpose over the 4 lanes of a quad (j = lane & 3): lane j's element s becomes lane
+// s's element j, in two exchanges (lane ^ 1, lane ^ 2)
+ISG_DEV float quad_xchg(float v, bool hi) {
+    const int x = __builtin_bit_cast(int, v);
+    const int a = __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false);
+    const int b = __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);
+    return __builtin_bit_cast(float, hi ? b : a);
+}
+ISG_DEV f32x4 quad_transpose(f32x4 v, int j) {
+    const bool b0 = (j & 1) != 0, b1 = (j & 2) != 0;
+#pragma unroll
+    for (int c = 0; c < 4; c += 2) {
+        const float got = quad_xchg(b0 ? v[c] : v[c + 1], false);
+        v[c] = b0 ? got : v[c];
+        v[c + 1] = b0 ? v[c + 1] : got;
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float got = quad_xchg(b1 ? v[c] : v[c + 2], true);
+        v[c] = b1 ? got : v[c];
+        v[c + 2] = b1 ? v[c + 2] : got;
+    }
+    return v;
+}
+
+// Where channel k of a chunk sits in As (column) and Xs (row): the two 2-bit fields of k mod 16
+// swapped. pw_mfma_span's step j gives lane slot kk position g + 4kk + j, which is then channel
+// g + 4j + kk: K is reduced in ascending order, the chunked pw_kernel's order, so a layer moved
+// here from pw_kernel keeps its results bit for bit.
+ISG_DEV int pwp_pos(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
+
+// The BatchNorm-backward rebuild with every product rounded before the sums, as pw_kernel's
+// ch_xform_u compiles (two products of one packed multiply, then the adds): left to the
+// compiler the branch-free form fuses a product into an FMA and the last bit of 1 value in 5
+// moves. Pinned here (tests/test_gpu_pw_wide.py holds pwp to pw_kernel's bits).
+ISG_DEV float bn_bwd_rounded(const ChanCoef& k, float x, float y) {
+#pragma clang fp contract(off)
+    const float a = k.c0 * x, b = k.c1 * (y - k.c2);
+    return (a + b) + k.c3;
+}
+
+// Issue the loads of the chunk at channel kc: 64 channels x 16 pixel quads (4 per lane,
+// clamped duplicates past K) and the BM x 64 weight slice as 16-B loads along whichever of
+// m / k is contiguous. Forward: row cr + 16u, k quad q. Input gradient: a lane quad covers
+// 4 k of one m quad, k = kc + 16u + 4 * (tid & 3) + wave, m quad (tid >> 2) & 15. Either way a
+// lane quad's 4 x 4 values are transposed in registers on the way into As (pwp_pos).
+template <bool HY>
+ISG_DEV void pwp_issue(PwpRegs<HY>& r, const PwxArgs& a, const VtSel vs, const PwpLane l, int kc,
+                       const float* __restrict__ w) {
+    const int K = a.K;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const ChSrc t = ch_addr(vs, min(kc + l.cr + 16 * u, K - 1), a.HW);
+        r.x[u] = gld4(t.p, (int64_t)l.n * t.ns + l.pix);
+        if constexpr (HY) r.y[u] = gld4(t.y, (int64_t)l.n * t.yns + l.pix);
+    }
+    const bool wk = a.wmode == 1;
+    const int j = l.tid & 3, mq = (l.tid >> 2) & 15, wv = l.tid >> 6;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int o1 = (l.m0 + min(l.cr + 16 * u, l.Mb - 1)) * a.rs + min(kc + 4 * l.q, K - 4);
+        const int o2 = min(kc + 16 * u + 4 * j + wv, K - 1) * a.cs + l.m0 + min(4 * mq, l.Mb - 4);
+        r.w[u] = gld4(w, wk ? o1 : o2);
+    }
+}
+
+// The chunk's registers into LDS: the producer transform on the way into Xs (the channel
+// differs between lanes: XfLin), zeros past K, past the problem's pixels and past Mb rows
+template <int TPW, bool HY>
+ISG_DEV void pwp_store(const PwpRegs<HY>& r, const PwxArgs& a, const VtSel vs, const PwpLane l, int kc,
+                       const ChanCoef* tabK, float* As, float* Xs) {
+    constexpr int BM = 16 * TPW;
+    const int K = a.K;
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int row = l.cr + 16 * u, c = kc + row;
+        const int cc = min(c, K - 1);
+        int cl;
+        const int s = vt_seg(vs, cc, cl);
+        const XfLin xl = xf_lin(ISG_SEL3(s, xf, vs), ISG_SEL3(s, act, vs), tabK[cc]);
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (HY) {
+                const float f = xf_lin_apply(xl, r.x[u][e], r.y[u][e]);
+                o[e] = xl.isb != 0.f ? bn_bwd_rounded(xl.k, r.x[u][e], r.y[u][e]) : f;
+            } else {
+                o[e] = xf_lin_apply(xl, r.x[u][e], r.x[u][e]);
+            }
+        }
+        *reinterpret_cast<f32x4*>(&Xs[pwp_pos(row) * kPpXS + 4 * l.q]) = (c < K && l.pv) ? o : zero;
+    }
+    if (a.wmode == 1) {
+#pragma unroll
+        for (int u = 0; u < TPW; ++u) {
+            // the lane quad holds 16 consecutive k of row m: after the transpose lane a has
+            // k = 16G + 4s + a (s = 0..3), the 4 consecutive positions 16G + 4a + s
+            f32x4 t = quad_transpose(r.w[u], l.q & 3);
+            const int row = l.cr + 16 * u, kb = kc + 16 * (l.q >> 2) + (l.q & 3);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = (kb + 4 * e < K && row < l.Mb) ? t[e] : 0.f;
+            *reinterpret_cast<f32x4*>(&As[row * kPpAS + 4 * l.q]) = t;
+        }
+    } else {
+        const int j = l.tid & 3, mq = (l.tid >> 2) & 15, wv = l.tid >> 6;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            // row m = 4 mq + j, k = 16u + 4s + wv (s = 0..3): positions 16u + 4 wv + s
+            f32x4 t = quad_transpose(r.w[u], j);
+            const int row = 4 * mq + j, kb = kc + 16 * u + wv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = (kb + 4 * e < K && row < l.Mb) ? t[e] : 0.f;
+            if (row < BM) *reinterpret_cast<f32x4*>(&As[row * kPpAS + 16 * u + 4 * wv]) = t;
+        }
+    }
+}
+
+template <int TPW, bool HY>
+__global__ __launch_bounds__(kThreads, 2) void pwp_kernel(PwxArgs a) {
+    constexpr int BM = 16 * TPW;
+    static_assert(BM <= kPpMaxBM, "pwp: at most 64 rows");
+    extern __shared__ f32x4 pwp_smem[];
+    char* const smem = reinterpret_cast<char*>(pwp_smem);
+    ChanCoef* const tabK = reinterpret_cast<ChanCoef*>(smem);
+    RowInfo* const ri = reinterpret_cast<RowInfo*>(smem + kPpOffRi);
+    float* const As = reinterpret_cast<float*>(smem + kPpOffA);  // [2][BM][kPpAS]
+    float* const Xs = As + 2 * BM * kPpAS;                        // [2][kPpKC][kPpXS]
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = wave_id();
+    const int kk = lane >> 4, pl = lane & 15;
+    const int K = a.K;
+    const float* __restrict__ w = a.w;
+    PwpLane l;
+    l.tid = tid; l.q = tid & 15; l.cr = tid >> 4;
+    l.m0 = blockIdx.y * BM;
+    l.Mb = min(BM, a.M - l.m0);
+    const int m0 = l.m0, Mb = l.Mb;
+    const int64_t p0 = (int64_t)blockIdx.x * kBP;
+    {
+        const int64_t pg = p0 + 4 * l.q;
+        l.pv = pg < a.P;
+        l.n = l.pv ? (int)((uint32_t)pg / (uint32_t)a.HW) : 0;  // P < 2^31 (host check)
+        l.pix = l.pv ? (int)pg - l.n * a.HW : 0;
+    }
+
+    if (!a.fast) {  // fp64 evaluation from the statistics (eval / direct ABI calls)
+        for (int c = tid; c < K; c += kThreads) tabK[c] = vt_coef(a.src, c);
+        for (int r = tid; r < Mb; r += kThreads) {
+            const SinkRow q = sink_row(a.out, m0 + r, a.HW);
+            RowInfo& d = ri[r];
+            d.p = q.p; d.y = q.y; d.ns = (int)q.ns; d.yns = (int)q.yns;
+            d.mode = q.mode; d.act = q.act; d.bias = q.bias; d.f = q.f;
+        }
+    }
+    // ---- the prologue round trip: chunk 0's loads lead it, then the records ---------------
+    const VtSel vs = vt_sel(a.src);
+    const SkSel ks = sk_sel(a.out);
+    PwpRegs<HY> rg;
+    pwp_issue<HY>(rg, a, vs, l, 0, w);
+    const bool stat_on = a.stat_on != 0;
+    const CoefLoad<HY ? 4 : 2> cfl = coef_issue<HY ? 4 : 2>(vs, min(tid, K - 1), stat_on);
+    const SinkLoad skl = sink_issue(ks, m0 + min(tid, Mb - 1), w, stat_on);
+    if (a.fast) {
+        if (tid < K) tabK[tid] = coef_finish(vs, tid, cfl);
+        if (tid < Mb) {
+            const SinkRow sq = sink_finish(ks, m0 + tid, a.HW, skl);
+            RowInfo& d = ri[tid];
+            d.p = sq.p; d.y = sq.y; d.ns = (int)sq.ns; d.yns = (int)sq.yns;
+            d.mode = sq.mode; d.act = sq.act; d.bias = sq.bias; d.f = sq.f;
+        }
+    }
+    if (tid >= Mb && tid < BM) ri[tid].mode = -1;
+    __syncthreads();  // the coefficient table, for the transform
+    pwp_store<TPW, HY>(rg, a, vs, l, 0, tabK, As, Xs);
+    __syncthreads();
+
+    // ---- K loop: tile i of wave w = row tile i, pixel tile w ------------------------------
+    int aoff[TPW], boff[TPW];
+#pragma unroll
+    for (int i = 0; i < TPW; ++i) {
+        aoff[i] = (i * 16 + pl) * kPpAS + 4 * kk;
+        boff[i] = (4 * kk) * kPpXS + wave * 16 + pl;
+    }
+    f32x4 acc[TPW];
+#pragma unroll
+    for (int i = 0; i < TPW; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nc = (K + kPpKC - 1) / kPpKC;
+    for (int c = 0; c + 1 < nc; ++c) {
+        const int cur = c & 1;
+        pwp_issue<HY>(rg, a, vs, l, (c + 1) * kPpKC, w);
+        __builtin_amdgcn_sched_barrier(0);  // the loads stay ahead of the MFMA pass
+        pw_mfma_span<TPW>(As + cur * BM * kPpAS, Xs + cur * kPpKC * kPpXS, aoff, boff, kPpKC, kPpXS, acc);
+        __builtin_amdgcn_sched_barrier(0);
+        pwp_store<TPW, HY>(rg, a, vs, l, (c + 1) * kPpKC, tabK, As + (cur ^ 1) * BM * kPpAS,
+                           Xs + (cur ^ 1) * kPpKC * kPpXS);
+        __syncthreads();  // the one barrier of the chunk: buffer cur consumed, cur ^ 1 staged
+    }
+    {
+        const int cur = (nc - 1) & 1;
+        const int kn = (K - (nc - 1) * kPpKC + 15) & ~15;
+        pw_mfma_span<TPW>(As + cur * BM * kPpAS, Xs + cur * kPpKC * kPpXS, aoff, boff, kn, kPpXS, acc);
+    }
+
+    // ---- epilogue: the generic (multi-sink) form -------------------------------------------
+    float pre[TPW][4];
+#pragma unroll
+    for (int i = 0; i < TPW; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) pre[i][r] = 0.f;
+    const TilePx e = tile_px(p0, wave, pl, a.P, a.HW);
+    if (a.pre_on) {
+#pragma unroll
+        for (int i = 0; i < TPW; ++i) tile_sink_operands(ri, i, kk, e, w, pre[i]);
+    }
+    const bool need_red = sinks_need_red(a.out);
+    float (*red)[4][kMaxBM] = reinterpret_cast<float (*)[4][kMaxBM]>(Xs);
+    if (need_red) {
+        __syncthreads();  // every wave is past its Xs reads
+        for (int i = tid; i < 4 * 4 * kMaxBM; i += kThreads) (&red[0][0][0])[i] = 0.f;
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < TPW; ++i) {
+        if (i * 16 >= Mb) continue;  // wave-uniform
+        float s0[4], s1[4], s2[4];
+        tile_to_sinks(ri, i, kk, e, acc[i], pre[i], s0, s1, s2);
+        if (need_red) tile_red(red, wave, i, kk, pl, Mb, s0, s1, s2);
+    }
+    if (need_red) {
+        __syncthreads();
+        for (int rl = tid; rl < Mb; rl += kThreads) {
+            red_fold(red, rl);
+            sink_row_flush(a.out, m0 + rl, red[0][0][rl], red[0][1][rl], red[0][2][rl]);
+        }
+    }
+}
+
+template <int TPW, bool HY>
+int32_t pwp_launch(const PwxArgs& a, dim3 grid, hipStream_t st) {
+    auto k = pwp_kernel<TPW, HY>;
+    static bool attr = false;
+    if (!attr) {
+        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, pwp_lds(64)) != hipSuccess)
+            return isg_check_launch("pwp_kernel: dynamic LDS");
+        attr = true;
+    }
+    hipLaunchKernelGGL(k, grid, dim3(kThreads), pwp_lds(16 * TPW), st, a);
+    return isg_check_launch("pwp_kernel");
+}
+template <bool HY>
+int32_t pwp_dispatch(const PwxArgs& a, dim3 grid, int tpw, hipStream_t st) {
+    switch (tpw) {
+        case 1: return pwp_launch<1, HY>(a, grid, st);
+        case 2: return pwp_launch<2, HY>(a, grid, st);
+        case 3: return pwp_launch<3, HY>(a, grid, st);
+        default: return pwp_launch<4, HY>(a, grid, st);
+    }
 }
 
 int pwx_align16(int v) { return (v + 15) & ~15; }
@@ -1058,8 +1382,17 @@ int32_t isg_pw_gemm(const isg_conv_geom* g, const isg_vtensor* src, const float*
     // 32 x 32 tiles — step 3.654 -> 3.680 ms, 3.573 -> 3.595 eager: kept on the chunked kernel)
     const bool slab_pays = res || (!dgrad && a.P >= 65536) || (dgrad && a.M <= 64 && a.K <= 128) ||
                            (!dgrad && a.M <= 64 && a.K <= 128) || (a.M <= 128 && a.K <= 64);
-    if (slab_pays && wmode && pwx_src_ok(*src, a.HW) && a.P < ((int64_t)1 << 31)) {
-        PwxArgs b{};
+    // what pwx and pwp both need: 16-B loads of every source row and of the weights
+    const bool aligned = wmode && pwx_src_ok(*src, a.HW) && a.P < ((int64_t)1 << 31);
+    // Aligned layers the slab does not pay for, whose K has no whole-K slab at 64 pixels
+    // (K > 128: 8 loads x 16 channel rows per lane), go to the K-pipelined kernel; narrower
+    // ones stay on the chunked kernel. ISG_PW_KERNEL=pwp hands any aligned layer to pwp and
+    // =pw keeps the chunked kernel (read per call: the tests and the A/B run both paths).
+    const char* pe = getenv("ISG_PW_KERNEL");
+    const bool force_pwp = pe && !strcmp(pe, "pwp"), force_pw = pe && !strcmp(pe, "pw");
+    PwxArgs b{};
+    bool hy = false;
+    if (aligned) {
         b.src = a.src; b.out = a.out; b.w = w; b.rs = a.rs; b.cs = a.cs;
         b.HW = a.HW; b.M = a.M; b.K = a.K; b.Kp = (a.K + 15) / 16 * 16; b.P = a.P;
         b.wmode = wmode;
@@ -1074,13 +1407,35 @@ int32_t isg_pw_gemm(const isg_conv_geom* g, const isg_vtensor* src, const float*
         // finalised by the consumer needs them even when its y is its own input (ADVICE r03:
         // the 2-group form would apply identity coefficients there)
         // HY also loads a BN_FWD segment's residual term (isg_vseg residual form)
-        bool hy = false;
         for (int s = 0; s < src->nseg; ++s) {
             if (src->s[s].xform == ISG_XF_BN_BWD &&
                 ((src->s[s].y && src->s[s].y != src->s[s].p) || (!src->s[s].bn.coef && src->s[s].bn.stats)))
                 hy = true;
             if (src->s[s].xform == ISG_XF_BN_FWD && src->s[s].y) hy = true;
         }
+    }
+    static const bool log = getenv("ISG_PWX_LOG") != nullptr;  // diagnostics: the chosen kernel and tiling
+    if (force_pwp || (aligned && !slab_pays && !force_pw && a.K > 128)) {
+        if (!aligned)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "pw gemm: the K-pipelined kernel needs 16-B aligned rows "
+                                 "and weights, HW %% 4 == 0");
+        if (res)
+            return isg_set_error(ISG_ERR_UNSUPPORTED, "pw gemm: residual form off the slab kernel "
+                                 "(the K-pipelined kernel takes no residual term, materialised input or "
+                                 "residual BatchNorm)");
+        // rows per block: up to 64, halved while that keeps more workgroups in flight
+        // (measured: DESIGN 3.4)
+        const int64_t pblocks = (a.P + kBP - 1) / kBP;
+        int bm = std::min(kPpMaxBM, (a.M + 15) / 16 * 16);
+        while (bm > 16 && pblocks * ((a.M + bm - 1) / bm) < kPwpMinBlocks) bm = (bm / 2 + 15) / 16 * 16;
+        b.BM = bm;
+        const dim3 grid((unsigned)pblocks, (unsigned)((a.M + bm - 1) / bm));
+        if (log)
+            fprintf(stderr, "pwp %s M %d K %d P %lld BM %d BP %d TPW %d HY %d blocks %lld\n", dgrad ? "dgrad" : "fwd",
+                    a.M, a.K, (long long)a.P, bm, kBP, bm / 16, (int)hy, (long long)(pblocks * grid.y));
+        return hy ? pwp_dispatch<true>(b, grid, bm / 16, st) : pwp_dispatch<false>(b, grid, bm / 16, st);
+    }
+    if (slab_pays && aligned) {
         // (BM, BP): rows first (fewer row blocks = fewer slab re-reads), then pixels; the
         // first configuration that fits the LDS and the per-lane load budget (8 weight and
         // 8 activation loads of 16 B), keeps >= 4 MFMA tiles per workgroup and gives >= 256
@@ -1125,7 +1480,6 @@ int32_t isg_pw_gemm(const isg_conv_geom* g, const isg_vtensor* src, const float*
             const dim3 grid((unsigned)((a.P + best_bp - 1) / best_bp), (unsigned)((a.M + best_bm - 1) / best_bm));
             int32_t rc;
             const bool seg1 = src->nseg == 1 && out->nsink == 1;
-            static const bool log = getenv("ISG_PWX_LOG") != nullptr;  // diagnostics: the chosen tiling
             if (log)
                 fprintf(stderr, "pwx %s M %d K %d P %lld BM %d BP %d TPW %d HY %d SEG1 %d RES %d blocks %lld\n",
                         dgrad ? "dgrad" : "fwd", a.M, a.K, (long long)a.P, best_bm, best_bp, tpw, (int)hy,
