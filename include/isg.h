@@ -480,6 +480,64 @@ int32_t isg_mask_rle_decode(const uint32_t* runs, int64_t runs_cap,
                             int32_t H, int32_t W, uint8_t* masks /* [n,H,W] */,
                             int64_t* totals /* [n] */, void* work, isg_stream_t stream);
 
+/* The COCO `counts` string of every slot, with its box and area (csrc/mask_rle_string.hip;
+ * the contract is stated on the CPU by instancesegmentation_amd/rle.py `compress` and
+ * `summarize`). isg_mask_rle's runs / offsets / runs_cap plug in unchanged. Slot j < n turns
+ * the counts c = runs[offsets[j] .. offsets[j+1]) into the bytes
+ * chars[char_offsets[j] .. char_offsets[j+1]), slots packed in slot order from 0: count i is
+ * written as v = c_i (i <= 2) or c_i - c_{i-2} (signed, 64 bits) in the fewest n of 1..7
+ * groups with -2^(5n-1) <= v < 2^(5n-1), group k = (((v >> 5k) & 31) | (k < n-1 ? 32 : 0))
+ * + 48. boxes[j] = [x, y, w, h], the tight box of the canvas isg_mask_rle_decode gives for
+ * the slot (runs clipped at H*W, zero-length runs stepped over, a set run across a column
+ * seam spans y = 0..H-1, [0,0,0,0] without a set pixel), areas[j] its set pixels.
+ * A slot whose range is empty or reversed, starts below 0 or reaches past runs_cap is void:
+ * no characters, box [0,0,0,0], area 0; runs at index >= runs_cap are never read. Slots may
+ * overlap or repeat. offsets: device memory.
+ * Overflow: all n + 1 char_offsets always hold the true values; chars[i] is written only for
+ * i < chars_cap (chars may be NULL when chars_cap == 0, at any byte address otherwise); boxes
+ * and areas do not depend on it. Nothing is raised on the device.
+ * Refused with ISG_ERR_INVALID before any HIP call: n < 0, a capacity < 0, H <= 0, W <= 0,
+ * H*W >= 2^31, a NULL pointer that would be used (runs may be NULL when runs_cap == 0),
+ * offsets / char_offsets / areas / work not 8-B aligned, runs / boxes not 4-B aligned. A
+ * capacity >= 2^31 is ISG_ERR_UNSUPPORTED. n == 0 does nothing.
+ * Capturable: the launch geometry depends on n only (one workgroup per slot, which walks its
+ * slot in chunks of isg_rle_string_chunk() counts), nothing is allocated or synchronised, and
+ * no result depends on what chars, char_offsets, boxes, areas or work held.
+ * work: isg_rle_compress_workspace(n, runs_cap) bytes (-1 for sizes the call refuses). */
+int32_t isg_rle_string_chunk(void);
+int64_t isg_rle_compress_workspace(int32_t n, int64_t runs_cap);
+int32_t isg_rle_compress(const uint32_t* runs, int64_t runs_cap,
+                         const int64_t* offsets /* [n+1], device */, int32_t n, int32_t H,
+                         int32_t W, uint8_t* chars, int64_t chars_cap,
+                         int64_t* char_offsets /* [n+1] */, int32_t* boxes /* [n][4] */,
+                         int64_t* areas /* [n] */, void* work, isg_stream_t stream);
+
+/* `counts` strings back to counts (csrc/mask_rle_string.hip; the contract is stated on the
+ * CPU by instancesegmentation_amd/rle.py `parse_total`): the inverse of isg_rle_compress,
+ * whose chars / char_offsets plug in unchanged, and the feeder of isg_mask_rle_decode, which
+ * takes runs / offsets / runs_cap as they come out. Slot j < n reads the bytes
+ * chars[char_offsets[j] .. char_offsets[j+1]) as g = (byte - 48) & 63; a byte with
+ * g & 32 == 0 ends a count, so the slot has as many counts as terminators, written to
+ * runs[offsets[j] .. offsets[j+1]), slots packed in slot order from 0. A count of k groups is
+ * worth its last min(k, 7): the sum of (g & 31) << 5m, lowest first, sign-extended from bit
+ * 5 min(k, 7) when the terminator has g & 16; count i >= 3 adds count i - 2 (64 bits,
+ * wrapping); the low 32 bits are stored. status[j] is the OR of 1 TRUNCATED (the last byte
+ * continues; its groups yield no count), 2 BAD_CHAR (a byte outside 48..111), 4 TOO_LONG (a
+ * count of more than 7 groups), 8 RANGE (a count outside [0, 2^32)); the caller judges,
+ * nothing is raised on the device.
+ * A slot whose range is empty or reversed, starts below 0 or reaches past chars_cap is void:
+ * no counts, status 0; chars at index >= chars_cap are never read. Slots may overlap.
+ * Overflow: all n + 1 offsets always hold the true values; runs[i] is written only for
+ * i < runs_cap (runs may be NULL when runs_cap == 0); status does not depend on it.
+ * Refusals, n == 0 and capturability as isg_rle_compress (8-B: char_offsets, offsets, work;
+ * 4-B: runs, status; chars at any byte).
+ * work: isg_rle_parse_workspace(n, chars_cap) bytes (-1 for sizes the call refuses). */
+int64_t isg_rle_parse_workspace(int32_t n, int64_t chars_cap);
+int32_t isg_rle_parse(const uint8_t* chars, int64_t chars_cap,
+                      const int64_t* char_offsets /* [n+1], device */, int32_t n,
+                      uint32_t* runs, int64_t runs_cap, int64_t* offsets /* [n+1] */,
+                      int32_t* status /* [n] */, void* work, isg_stream_t stream);
+
 /* ---- scoring (csrc/mask_eval.hip) ------------------------ */
 
 /* Crop-space validation IoU counts (the contract is stated on the CPU by

@@ -23,6 +23,9 @@ LIST_CHUNK = 32
 STAT_REP = int(os.environ.get("ISG_STAT_REP", "4"))  # accumulator replicas (isg.h ISG_STAT_REP)
 ABI_VERSION = 14
 WREP = int(os.environ.get("ISG_WREP", "16"))  # weight-gradient replicas (isg.h ISG_WREP)
+# counts (bytes) one workgroup of isg_rle_compress (isg_rle_parse) takes per round
+# (csrc/mask_rle_string.hip kChunk; checked against isg_rle_string_chunk() on load)
+RLE_STRING_CHUNK = 2048
 
 
 class Bn(Structure):
@@ -244,6 +247,14 @@ SIGNATURES = {
     "isg_mask_rle_decode_workspace": (c_int64, [c_int32, c_int32, c_int32, c_int64]),
     "isg_mask_rle_decode": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isg_rle_string_chunk": (c_int32, []),
+    "isg_rle_compress_workspace": (c_int64, [c_int32, c_int64]),
+    "isg_rle_compress": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32,
+                                   c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "isg_rle_parse_workspace": (c_int64, [c_int32, c_int64]),
+    "isg_rle_parse": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
     "isg_mask_iou_crops": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p,
                                      c_void_p]),
     "isg_mask_iou_matrix_workspace": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
@@ -297,6 +308,9 @@ def lib():
             raise RuntimeError(f"ABI mismatch: libisg.so is version {h.isg_abi_version()} "
                                f"with {h.isg_stat_replicas()} stat replicas, expected "
                                f"{ABI_VERSION} / {STAT_REP}; rebuild it")
+        if h.isg_rle_string_chunk() != RLE_STRING_CHUNK:
+            raise RuntimeError(f"ABI mismatch: isg_rle_string_chunk() is "
+                               f"{h.isg_rle_string_chunk()}, expected {RLE_STRING_CHUNK}")
         for which, cls in _RECORD_CHECK:
             n = h.isg_record_size(which)
             if n != ctypes.sizeof(cls):

@@ -285,10 +285,20 @@ def _counts_u32(counts):
     return np.ascontiguousarray(c.astype(np.uint32))
 
 
+class RleStringError(ValueError):
+    """A `counts` string isg_rle_parse flagged: `mask` is its index in the call, `reason`
+    the words of rle.status_text."""
+
+    def __init__(self, mask, reason):
+        super().__init__(f"mask {mask}: {reason}")
+        self.mask, self.reason = mask, reason
+
+
 class RleDecoder:
     """isg_mask_rle_decode for images of one size: owns the runs, offsets, totals, workspace
     and canvas buffers for up to max_masks masks of max_counts counts together (rle.py
-    `decode_canvas` is the CPU statement)."""
+    `decode_canvas` is the CPU statement). decode_strings takes the `counts` strings
+    themselves and parses them on the device too (isg_rle_parse, rle.py `parse_total`)."""
 
     def __init__(self, image_hw, max_masks, max_counts, device=None):
         import torch
@@ -346,6 +356,65 @@ class RleDecoder:
                              f"{self.H * self.W}")
         return self.masks[:n]
 
+    def decode_strings(self, strings, strict=True):
+        """strings: a list of COCO `counts` strings (str or bytes), one per mask -> what
+        `decode` returns for their counts, without a host codec: the concatenated bytes and
+        their offsets go up, isg_rle_parse fills the decoder's own runs / offsets,
+        isg_mask_rle_decode reads them, and one copy brings totals and status back. A
+        string the parser flags raises RleStringError (a ValueError) naming the mask and the
+        reason, a truncated one in rle.from_string's words."""
+        import torch
+
+        from . import _lib as L
+        from .rle import status_text
+        per = [np.frombuffer(s.encode("latin-1") if isinstance(s, str) else bytes(s), np.uint8)
+               for s in strings]
+        n = len(per)
+        if n > self.max_masks:
+            raise ValueError(f"{n} masks > capacity {self.max_masks}")
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(b) for b in per])
+        nbytes = int(off[-1])
+        flat = np.concatenate(per) if nbytes else np.zeros(0, np.uint8)
+        # a mask has at most as many counts as bytes; only past that bound are they counted
+        if nbytes > self.max_counts:
+            total = int(np.count_nonzero(((flat - np.uint8(48)) & np.uint8(0x20)) == 0))
+            if total > self.max_counts:
+                raise ValueError(f"{total} counts > capacity {self.max_counts}")
+        if n == 0:
+            empty = np.zeros(0, np.int64)
+            return self.masks[:0] if strict else (self.masks[:0], empty)
+        if nbytes >= 2 ** 31:
+            raise ValueError(f"{nbytes} characters in one call (max 2^31 - 1)")
+        lib, dev, st = L.lib(), self.device, L.stream_ptr(self.device)
+        if getattr(self, "_chars", None) is None or self._chars.numel() < nbytes:
+            self._chars = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        if getattr(self, "_char_offsets", None) is None:  # first use: the parser's buffers
+            self._char_offsets = torch.empty(self.max_masks + 1, dtype=torch.int64, device=dev)
+            self._parse_work = torch.empty(max(self.max_masks, 1), dtype=torch.int64, device=dev)
+            self._status = torch.empty(max(self.max_masks, 1), dtype=torch.int32, device=dev)
+        if nbytes:
+            self._chars[:nbytes].copy_(torch.from_numpy(flat.copy()))
+        self._char_offsets[:n + 1].copy_(torch.from_numpy(off))
+        L.check(lib.isg_rle_parse(self._chars.data_ptr(), nbytes, self._char_offsets.data_ptr(), n,
+                                  self.runs.data_ptr(), self.max_counts, self.offsets.data_ptr(),
+                                  self._status.data_ptr(), self._parse_work.data_ptr(), st),
+                "rle_parse")
+        L.check(lib.isg_mask_rle_decode(self.runs.data_ptr(), self.max_counts,
+                                        self.offsets.data_ptr(), n, self.H, self.W,
+                                        self.masks.data_ptr(), self.totals.data_ptr(),
+                                        self.work.data_ptr(), st), "mask_rle_decode")
+        back = torch.cat([self.totals[:n].view(torch.int32), self._status[:n]]).cpu().numpy()
+        totals, status = back[:2 * n].view(np.int64).copy(), back[2 * n:]
+        for j in np.flatnonzero(status):
+            raise RleStringError(int(j), status_text(int(status[j])))
+        if not strict:
+            return self.masks[:n], totals
+        for j in np.flatnonzero(totals != self.H * self.W):
+            raise ValueError(f"mask {int(j)}: counts sum to {int(totals[j])}, not H*W = "
+                             f"{self.H * self.W}")
+        return self.masks[:n]
+
 
 # ---- scoring an existing results.json ---------------------------------------------------
 def group_detections(results, image_paths):
@@ -386,6 +455,15 @@ def segmentation_counts(seg, H, W):
     return from_string(c) if isinstance(c, (str, bytes)) else _counts_u32(c)
 
 
+def segmentation_source(seg, H, W):
+    """As segmentation_counts, with a compressed `counts` string left as it is (bytes) for
+    RleDecoder.decode_strings: its length bounds its number of counts."""
+    c = seg.get("counts") if isinstance(seg, dict) else None
+    if isinstance(c, (str, bytes)) and "size" in seg and [int(v) for v in seg["size"]] == [H, W]:
+        return c.encode("latin-1") if isinstance(c, str) else bytes(c)
+    return segmentation_counts(seg, H, W)
+
+
 DECODE_MASKS = 16  # masks one decode / match round holds (the matcher's max_det)
 
 
@@ -412,7 +490,7 @@ def score_results(results_path, image_dir, mask_root=None, device=None):
         with Image.open(path) as im:
             W, H = im.size
         dets = groups[path]
-        counts = [segmentation_counts(r["segmentation"], H, W) for r in dets]
+        counts = [segmentation_source(r["segmentation"], H, W) for r in dets]
         gt, gt_index = load_ground_truth(os.path.splitext(path)[0] + ".json", mask_root, H, W)
         matcher = matchers.get((H, W))
         if matcher is None or matcher.max_gt < len(gt):
@@ -430,7 +508,20 @@ def score_results(results_path, image_dir, mask_root=None, device=None):
                    and (e == k or used + len(counts[e]) <= dec.max_counts)):
                 used += len(counts[e])
                 e += 1
-            canvases, totals = dec.decode(counts[k:e], strict=False)
+            name = os.path.basename(path)
+            if all(isinstance(c, bytes) for c in counts[k:e]):  # parsed on the device
+                try:
+                    canvases, totals = dec.decode_strings(counts[k:e], strict=False)
+                except RleStringError as err:
+                    raise ValueError(f"{name}, detection {k + err.mask}: {err.reason}") from None
+            else:
+                for d in range(k, e):
+                    if isinstance(counts[d], bytes):
+                        try:
+                            counts[d] = segmentation_counts(dets[d]["segmentation"], H, W)
+                        except ValueError as err:
+                            raise ValueError(f"{name}, detection {d}: {err}") from None
+                canvases, totals = dec.decode(counts[k:e], strict=False)
             for j in np.flatnonzero(totals != H * W):
                 raise ValueError(f"{os.path.basename(path)}, detection {k + int(j)}: counts sum to "
                                  f"{int(totals[j])}, not H*W = {H * W}")

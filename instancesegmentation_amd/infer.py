@@ -19,6 +19,8 @@ per-instance input path (train_instance.py:139-202, test branch) and model:
   keep     = greedy mask-NMS, IoU 0.5 (A14)
   rle      = (rle=True) the kept masks run-length encoded on the GPU, COCO order
              (csrc/mask_rle.hip, rle.py): a few KB leave the device instead of the canvases
+  strings  = (rle_strings=True) their COCO `counts` strings, boxes and areas, written on the
+             GPU as well (csrc/mask_rle_string.hip): the host slices bytes, no codec runs
 
 Everything after the host copy of the image runs on the GPU (csrc/infer_ops.hip,
 maskops.hip, the Segment plan) and is captured into one HIP graph per (image size,
@@ -82,10 +84,16 @@ class InstanceSegmenter:
     image_hw: (H, W) of the images this instance serves; max_instances: capacity K.
     rle=True appends the COCO run-length encoding of the kept masks to the pipeline
     (result_rle()); rle_capacity: uint32 counts the device buffer holds for all kept masks
-    of one image (default RLE_CAPACITY_FACTOR * K * (H + W))."""
+    of one image (default RLE_CAPACITY_FACTOR * K * (H + W)).
+    rle_strings=True (needs rle=True) appends the `counts` strings, boxes and areas of those
+    encodings (result_coco(); result_rle() then slices the strings instead of building
+    them); rle_chars_capacity: bytes the device buffer holds for all strings of one image
+    (default 2 * rle_capacity: a person's mask takes about one character per count, the
+    worst case is seven)."""
 
     def __init__(self, model, image_hw, max_instances=16, iou_thr=0.5, device=None,
-                 capture=True, rle=False, rle_capacity=None):
+                 capture=True, rle=False, rle_capacity=None, rle_strings=False,
+                 rle_chars_capacity=None):
         import copy
         self.device = torch.device(device or "cuda")
         if self.device.type != "cuda":
@@ -127,6 +135,24 @@ class InstanceSegmenter:
             self.rle_work = torch.empty(L.lib().isg_mask_rle_workspace(K, H, W),
                                         dtype=torch.uint8, device=dev)
             self._rle_warned = False
+        self.rle_strings = bool(rle_strings)
+        if self.rle_strings:
+            if not self.rle:
+                raise ValueError("rle_strings=True needs rle=True")
+            ccap = 2 * self.rle_capacity if rle_chars_capacity is None else int(rle_chars_capacity)
+            if ccap < 0:
+                raise ValueError(f"rle_chars_capacity {ccap} < 0")
+            self.rle_chars_capacity = ccap
+            self.rle_chars = torch.empty(max(ccap, 1), dtype=torch.uint8, device=dev)
+            # character offsets [K+1] and areas [K] (int64), boxes [K,4] (int32), back to
+            # back so that one copy brings them
+            self.rle_meta = torch.empty(2 * (K + 1) + 2 * K + 4 * K, dtype=torch.int32, device=dev)
+            self.rle_char_offsets = self.rle_meta[:2 * K + 2].view(torch.int64)
+            self.rle_areas = self.rle_meta[2 * K + 2:4 * K + 2].view(torch.int64)
+            self.rle_boxes = self.rle_meta[4 * K + 2:].view(K, 4)
+            self.rle_string_work = torch.empty(
+                L.lib().isg_rle_compress_workspace(K, self.rle_capacity) // 8, dtype=torch.int64,
+                device=dev)
         self.act = torch.empty(max(self.plan.act_size, 1), dtype=torch.float32, device=dev)
         self.stats = torch.empty(self.plan.stats_size, dtype=torch.float64, device=dev)
         g = self.plan.graph
@@ -171,6 +197,13 @@ class InstanceSegmenter:
                                      self.rle_runs.data_ptr(), self.rle_capacity,
                                      self.rle_offsets.data_ptr(), self.rle_work.data_ptr(), st),
                     "mask_rle")
+        if self.rle_strings:  # slots past *nkeep are empty ranges: no characters
+            L.check(lib.isg_rle_compress(self.rle_runs.data_ptr(), self.rle_capacity,
+                                         self.rle_offsets.data_ptr(), K, self.H, self.W,
+                                         self.rle_chars.data_ptr(), self.rle_chars_capacity,
+                                         self.rle_char_offsets.data_ptr(),
+                                         self.rle_boxes.data_ptr(), self.rle_areas.data_ptr(),
+                                         self.rle_string_work.data_ptr(), st), "rle_compress")
 
     def load(self, image, boxes, keypoints):
         """Copy one image's inputs into the static buffers (no launch).
@@ -220,6 +253,9 @@ class InstanceSegmenter:
         answer, one warning)."""
         if not self.rle:
             raise RuntimeError("result_rle() needs InstanceSegmenter(rle=True)")
+        if self.rle_strings:
+            segs, _, _, keep, scores = self._result_strings()
+            return segs, keep, scores
         K = self.K
         torch.cuda.synchronize(self.device)  # as result() does, before anything reads
         # the small results in one copy: offsets, keep, nkeep, scores
@@ -245,6 +281,57 @@ class InstanceSegmenter:
             segs.append({"size": [self.H, self.W], "counts": R.to_string(counts)})
             keep.append(int(i))
         return segs, keep, scores
+
+    def result_coco(self):
+        """(segmentations, boxes, areas, keep list, scores [n]) of the last run:
+        segmentations and keep as result_rle(), boxes[i] = [x, y, w, h] (ints, as
+        rle.to_bbox) and areas[i] the set pixels of mask keep[i]. Everything was written on
+        the device; two copies bring it. Masks whose counts or characters did not fit their
+        buffers take the CPU path (same answer, one warning)."""
+        if not self.rle_strings:
+            raise RuntimeError("result_coco() needs InstanceSegmenter(rle=True, rle_strings=True)")
+        return self._result_strings()
+
+    def _result_strings(self):
+        K, H, W = self.K, self.H, self.W
+        torch.cuda.synchronize(self.device)
+        # one copy: count offsets, character offsets, areas, boxes, keep, nkeep, scores
+        meta = torch.cat([self.rle_offsets.view(torch.int32), self.rle_meta, self.keep,
+                          self.nkeep, self.scores.view(torch.int32)]).cpu().numpy()
+        off = meta[:2 * K + 2].view(np.int64)
+        coff = meta[2 * K + 2:4 * K + 4].view(np.int64)
+        areas = meta[4 * K + 4:6 * K + 4].view(np.int64)
+        boxes = meta[6 * K + 4:10 * K + 4].reshape(K, 4)
+        slots = meta[10 * K + 4:11 * K + 4][:int(meta[11 * K + 4])].tolist()
+        scores = meta[11 * K + 5:].view(np.float32)[:self.n].copy()
+        total, cap = int(off[-1]), self.rle_capacity
+        ctotal, ccap = int(coff[-1]), self.rle_chars_capacity
+        chars = self.rle_chars[:min(ctotal, ccap)].cpu().numpy().tobytes()  # the second copy
+        if (total > cap or ctotal > ccap) and not self._rle_warned:
+            self._rle_warned = True
+            what = (f"{total} counts > rle_capacity {cap}" if total > cap
+                    else f"{ctotal} characters > rle_chars_capacity {ccap}")
+            warnings.warn(f"RLE buffer overflow: {what}; the masks that did not fit are encoded "
+                          "on the CPU", RuntimeWarning)
+        segs, out_boxes, out_areas, keep = [], [], [], []
+        for j, i in enumerate(slots):
+            if i >= self.n:  # padded slot
+                continue
+            if off[j + 1] <= cap and coff[j + 1] <= ccap:
+                counts = chars[coff[j]:coff[j + 1]].decode("ascii")
+                box, area = [int(v) for v in boxes[j]], int(areas[j])
+            else:
+                if off[j + 1] <= cap:
+                    c = self.rle_runs[int(off[j]):int(off[j + 1])].cpu().numpy().view(np.uint32)
+                else:
+                    c = R.encode(self.masks[i].cpu().numpy())
+                counts = R.to_string(c)
+                box, area = R.summarize(c, H, W)
+            segs.append({"size": [H, W], "counts": counts})
+            out_boxes.append(box)
+            out_areas.append(area)
+            keep.append(int(i))
+        return segs, out_boxes, out_areas, keep, scores
 
     def __call__(self, image, boxes, keypoints):
         self.load(image, boxes, keypoints)
@@ -385,7 +472,7 @@ def main(argv=None):
         eng = engines.get((H, W, cap))
         if eng is None:
             eng = engines[(H, W, cap)] = InstanceSegmenter(model, (H, W), cap, args.iou,
-                                                           rle=coco)
+                                                           rle=coco, rle_strings=coco)
         res = {"image": os.path.basename(filepath), "instances": len(boxes), "keep": [],
                "scores": []}
         if coco:
@@ -414,11 +501,15 @@ def main(argv=None):
                 if coco:
                     eng.load(img, boxes[b0:b0 + eng.K], kps[b0:b0 + eng.K])
                     eng.run()
-                    segs, keep, scores = eng.result_rle()
+                    if eng.rle_strings:  # strings and boxes as the device wrote them
+                        segs, bbox, _, keep, scores = eng.result_coco()
+                    else:
+                        segs, keep, scores = eng.result_rle()
+                        bbox = [R.to_bbox(R.from_string(sg["counts"]), H, W) for sg in segs]
                     res["keep"] += [b0 + i for i in keep]
                     res["scores"] += [float(s) for s in scores]
                     res["segmentation"] += segs
-                    res["bbox"] += [R.to_bbox(R.from_string(sg["counts"]), H, W) for sg in segs]
+                    res["bbox"] += bbox
                     if args.evaluate:
                         match(keep, scores)
                     continue

@@ -18,7 +18,9 @@ csrc/mask_eval.hip), at the sizes the project runs:
              RleDecoder.decode (packing, upload, kernels, the totals' copy back), wall clock;
              isg_mask_rle_decode alone by device events, with its share of the HBM rate for
              the canvas bytes it writes; and, on its own, rle.from_string over the same
-             masks' strings (the parse stays on the host).
+             masks' strings, and that parse followed by RleDecoder.decode against
+             RleDecoder.decode_strings (the strings parsed on the device, isg_rle_parse),
+             wall clock, with isg_rle_parse alone by device events.
     Rounds alternate the legs; every leg is warmed up first; the two answers of each pair
     are compared before anything is timed. Prints one JSON line. Needs the GPU: there is
     no fallback.
@@ -194,18 +196,44 @@ def main(argv=None):
                                             decoder.masks.data_ptr(), decoder.totals.data_ptr(),
                                             decoder.work.data_ptr(), L.stream_ptr(dev)))
 
-    times = {"host_ms": [], "device_ms": [], "from_string_ms": []}
+    def host_parse_device_decode():  # the offline scorer's path before decode_strings
+        return decoder.decode(parse_strings())
+
+    def device_parse_decode():
+        return decoder.decode_strings(strings)
+
+    assert torch.equal(device_parse_decode(), det_d)
+    nbytes = sum(len(s) for s in strings)
+
+    def parse_kernels():  # on what device_parse_decode() uploaded
+        L.check(L.lib().isg_rle_parse(decoder._chars.data_ptr(), nbytes,
+                                      decoder._char_offsets.data_ptr(), K, decoder.runs.data_ptr(),
+                                      decoder.max_counts, decoder.offsets.data_ptr(),
+                                      decoder._status.data_ptr(), decoder._parse_work.data_ptr(),
+                                      L.stream_ptr(dev)))
+
+    times = {"host_ms": [], "device_ms": [], "from_string_ms": [],
+             "from_string_then_decode_ms": [], "decode_strings_ms": []}
     wall_ms(host_decode, 1)
     wall_ms(device_decode, 3)
+    wall_ms(host_parse_device_decode, 1)
+    wall_ms(device_parse_decode, 3)
     event_ms(decode_kernels, 2)
-    ktime = []
+    event_ms(parse_kernels, 2)
+    ktime, ptime = [], []
     for _ in range(args.rounds):
         times["host_ms"].append(wall_ms(host_decode, 1))
         times["device_ms"].append(wall_ms(device_decode, args.reps))
         times["from_string_ms"].append(wall_ms(parse_strings, 1))
+        times["from_string_then_decode_ms"].append(wall_ms(host_parse_device_decode, 1))
+        times["decode_strings_ms"].append(wall_ms(device_parse_decode, args.reps))
         ktime.append(event_ms(decode_kernels, args.reps))
+        ptime.append(event_ms(parse_kernels, args.reps))
     dec = {k: stats(v) for k, v in times.items()}
     dec["kernels_ms"] = stats(ktime)
+    dec["parse_kernels_ms"] = stats(ptime)
+    dec["speedup_host_parse_over_decode_strings"] = round(
+        dec["from_string_then_decode_ms"]["median"] / dec["decode_strings_ms"]["median"], 2)
     dec["speedup_host_over_device"] = round(dec["host_ms"]["median"] / dec["device_ms"]["median"], 2)
     dec["counts"] = total
     dec["string_bytes"] = sum(len(s) for s in strings)
